@@ -9,10 +9,17 @@ Inputs (velocity model, observed data) are synthetic and resident in HBM before 
 
 value = shot-timesteps/s over the whole job = N * ns_per_gpu * nt * B / (step time, max over
 ranks).  Weak scaling.  N = 1: configs[1] (FlatVel-A, 8 shots).  N > 1: configs[3]'s shape
-(CurveFault-B, 32 shots per GPU: 256 over 8 GPUs); the N = 1 line also reports that per-rank
+(CurveFault-B, 32 shots per GPU: 256 over 8 GPUs); the N = 1 --full line also reports that per-rank
 workload on one GPU ("configs3_rank_workload") as the base of the scaling curve.
 
-  python bench.py [--gpus N] [--steps K] [--warmup W] [--ns S] [--family F] [--no-cpu-baseline]
+  python bench.py [--gpus N] [--steps K] [--warmup W] [--ns S] [--family F] [--dump-outputs DIR] [--full]
+
+A plain run sets up, warms up, times the K steps and prints the result line (metric, value,
+ms_per_step, the configuration and the kernels' launch geometry).  --dump-outputs DIR also writes
+what the last timed step computed (seismograms, loss, gradient, updated model) as DIR/<name>.npy.
+--full adds every other measurement to the line: phase timing and the roofline block, the
+InversionEngine per-iteration wallclock, the configs[2] / [3] / [4] workloads, the U-Net rates and
+the CPU baseline (each can be switched off by its --no-* option).
 
 --gpus N > 1 outside a torch.distributed launcher starts the N ranks itself (torch.distributed.run,
 one process per GPU, RCCL) as child processes; this parent never touches the GPU.
@@ -49,6 +56,11 @@ def parse():
     p.add_argument("--family", default=None, help="synthetic model family (default flatvel at N=1, curvefault at N>1)")
     p.add_argument("--nt", type=int, default=1000)
     p.add_argument("--batch", type=int, default=1)
+    p.add_argument("--full", action="store_true",
+                   help="also run every secondary measurement (phases + roofline, loop wallclock, configs[2]/[3]/[4], "
+                        "U-Net rates, CPU baseline); the --no-* options below trim a --full run")
+    p.add_argument("--dump-outputs", metavar="DIR", default=None,
+                   help="write the last timed step's outputs (seis, loss, grad, model) as DIR/<name>.npy, float32")
     p.add_argument("--no-cpu-baseline", action="store_true")
     p.add_argument("--no-loop", action="store_true", help="skip the InversionEngine per-iteration wallclock")
     p.add_argument("--cpu-sample-shots", type=int, default=4)
@@ -449,11 +461,13 @@ def main():
         v_in = mu[:, :, 1:-1, 1:-1]
         if distributed:
             v_in = grad_all_reduce(v_in)
-        loss = l1_misfit(fwi(v_in), y, None, nobs) + lam * total_variation_loss(mu)
+        seis = fwi(v_in)
+        loss = l1_misfit(seis, y, None, nobs) + lam * total_variation_loss(mu)
         opt.zero_grad()
         loss.sum().backward()
         opt.step()                                              # + clamp_(-1, 1)
         opt.lr = sched.step()
+        return seis, loss
 
     for _ in range(a.warmup):
         step()
@@ -461,8 +475,10 @@ def main():
         dist.barrier()
     torch.cuda.synchronize()
     t0 = time.perf_counter()
+    last = None
     for _ in range(a.steps):
-        step()
+        last = None      # the previous step's graph is released before the next step, as when step() returned nothing
+        last = step()
     torch.cuda.synchronize()
     if distributed:
         dist.barrier()
@@ -475,6 +491,57 @@ def main():
         print("after timed loop:", fwi._plan(70, 70, dev).debug_words(), file=sys.stderr, flush=True)
     fwi.check()          # raises if any persistent launch of the timed region gave up a hand-off
 
+    units = world * nsl * nt * B
+    out = {
+        "metric": METRIC, "value": round(units / t_step, 1), "unit": "shot-timesteps/s", "n_gpus": world,
+        "steps": a.steps, "warmup": a.warmup, "ms_per_step": round(t_step * 1e3, 4), "higher_is_better": True,
+        "scaling": "weak", "vs_baseline": None, "dtype": "f32", "data": "synthetic",
+        "config": {"workload": (("configs[1]: OpenFWI FlatVel-A" if (world == 1 and nsl == 8 and family == "flatvel")
+                                 else ("configs[3] shape: OpenFWI CurveFault-B" if (nsl == 32 and family == "curvefault")
+                                       else f"OpenFWI {family}")) +
+                                f" 70x70 (310x310 padded), {nsl} shots/GPU ({ns_tot} total), nt={nt}, "
+                                "fwd+adj gradient + TV + Adam step" +
+                                (f" + one {'RCCL' if backend == 'nccl' else backend} all-reduce of the model gradient"
+                                 if distributed else "")),
+                   "global_batch": B, "shots_per_gpu": nsl, "shots_total": ns_tot, "nt": nt,
+                   "parallelism": f"shot-parallel x{world}"},
+        "kernels": fwi._plan(70, 70, dev).launch_info(B),
+    }
+    if a.dump_outputs and rank == 0:
+        out["dumped_outputs"] = dump_outputs(a.dump_outputs, mu, *last)
+    if a.full:
+        full_measurements(out, a, fwi, mu, mu0, vt, vtrue, y, ctx, dev, world, rank, distributed, backend, nsl,
+                          t_step)
+    if rank == 0:
+        print(json.dumps(out), flush=True)
+    if distributed:
+        dist.destroy_process_group()
+
+
+DUMP_MAX_ELEMS = 12 * 2 ** 20     # per array (48 MiB of float32): the four arrays stay under 64 MB together
+
+
+def dump_outputs(d, mu, seis, loss):
+    """--dump-outputs: what a caller of the timed step holds after the last timed step, as
+    float32 DIR/<name>.npy: the predicted seismograms of this rank's shots, the per-model loss, the
+    gradient w.r.t. the padded model and the model after the Adam + clamp update.  An array above
+    DUMP_MAX_ELEMS is written as a fixed sample of its flattened elements (seed 0, sorted indices)."""
+    os.makedirs(d, exist_ok=True)
+    shapes = {}
+    for name, t in (("seis", seis), ("loss", loss), ("grad", mu.grad), ("model", mu)):
+        x = t.detach().to(torch.float32).cpu().numpy()
+        shapes[name] = list(x.shape)
+        if x.size > DUMP_MAX_ELEMS:
+            idx = np.sort(np.random.default_rng(0).choice(x.size, DUMP_MAX_ELEMS, replace=False))
+            x = x.reshape(-1)[idx]
+        np.save(os.path.join(d, name + ".npy"), x)
+    return shapes
+
+
+def full_measurements(out, a, fwi, mu, mu0, vt, vtrue, y, ctx, dev, world, rank, distributed, backend, nsl, t_step):
+    """--full: every measurement beside the headline figure, added to the result line `out`."""
+    B, nt = a.batch, a.nt
+    dbg = os.environ.get("RDQ_DEBUG_STATUS")
     # ---- phase timing with HIP events on the stream the graphs/kernels are launched on ----
     plan = fwi._plan(70, 70, dev)
     sz = plan.sizes(B)
@@ -532,20 +599,7 @@ def main():
         if tj.get("kernel") == kname:
             traffic = tj["traffic_bytes_per_launch"]
 
-    units = world * nsl * nt * B
-    out = {
-        "metric": METRIC, "value": round(units / t_step, 1), "unit": "shot-timesteps/s", "n_gpus": world,
-        "steps": a.steps, "warmup": a.warmup, "ms_per_step": round(t_step * 1e3, 4), "higher_is_better": True,
-        "scaling": "weak", "vs_baseline": None, "dtype": "f32", "data": "synthetic",
-        "config": {"workload": (("configs[1]: OpenFWI FlatVel-A" if (world == 1 and nsl == 8 and family == "flatvel")
-                                 else ("configs[3] shape: OpenFWI CurveFault-B" if (nsl == 32 and family == "curvefault")
-                                       else f"OpenFWI {family}")) +
-                                f" 70x70 (310x310 padded), {nsl} shots/GPU ({ns_tot} total), nt={nt}, "
-                                "fwd+adj gradient + TV + Adam step" +
-                                (f" + one {'RCCL' if backend == 'nccl' else backend} all-reduce of the model gradient"
-                                 if distributed else "")),
-                   "global_batch": B, "shots_per_gpu": nsl, "shots_total": ns_tot, "nt": nt,
-                   "parallelism": f"shot-parallel x{world}"},
+    out.update({
         "roofline": {"bound": "hbm", "kernel": kname, "achieved": round(achieved, 1), "peak": HBM_PEAK_GBS,
                      "unit": "GB/s", "frac": round(achieved / HBM_PEAK_GBS, 4), "traffic": traffic,
                      # the PMC-measured HBM bytes of the same launch over its time: what the memory system
@@ -562,7 +616,6 @@ def main():
                      "adj_us_per_timestep": round(adj_launch_us / steps_per_launch, 4),
                      "fwd_us_per_timestep": round(fw_ms * 1e3 / nt, 4),
                      "traffic_source": os.path.relpath(tfile, ROOT) if traffic is not None else None},
-        "kernels": info,
         "phases_ms": {"coeffs+forward": round(fw_ms, 3), "adjoint": round(adj_ms, 3),
                       "fwd_GBps_alg": round(fwd_bytes * nt / (fw_ms * 1e-3) / 1e9, 1)},
         "fwd_adj_only_shot_ts_per_s": round(nsl * nt * B / ((fw_ms + adj_ms) * 1e-3), 1),
@@ -571,7 +624,7 @@ def main():
                      # runs after the timed loop, so this can dip below 0 by the kernels' own
                      # launch-to-launch spread (about +-5 %)
                      "step_minus_kernel_phases_ms": round(t_step * 1e3 - fw_ms - adj_ms, 4)},
-    }
+    })
     if not a.no_loop:
         # per-iteration wallclock of the drop-in loop itself (InversionEngine.optimize with TV,
         # metrics and histories included), the metric's second half
@@ -609,10 +662,6 @@ def main():
         out["configs4_rank_workload"] = configs4_rank_workload(dev, a)
     if rank == 0 and world == 1 and not a.no_cpu_baseline:
         out["cpu_baseline"] = cpu_baseline(ctx, vtrue[:1], a.cpu_sample_shots, a.cpu_sample_reps)
-    if rank == 0:
-        print(json.dumps(out), flush=True)
-    if distributed:
-        dist.destroy_process_group()
 
 
 if __name__ == "__main__":

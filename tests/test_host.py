@@ -319,6 +319,42 @@ def test_bench_launches_n_ranks_itself(monkeypatch):
     assert seen["env"]["HSA_ENABLE_IPC_MODE_LEGACY"] == "0"
 
 
+def test_bench_dump_outputs_and_plain_run_options(tmp_path, monkeypatch):
+    """bench.py --dump-outputs: the four arrays of the last timed step as float32 .npy; an array
+    above the per-array cap is a fixed sample (same indices every run).  --full is off by default."""
+    import importlib.util
+    import sys
+    spec = importlib.util.spec_from_file_location("bench_mod", os.path.join(ROOT, "bench.py"))
+    bench = importlib.util.module_from_spec(spec)
+    spec.loader.exec_module(bench)
+    monkeypatch.setattr(sys, "argv", ["bench.py", "--gpus", "1", "--steps", "4", "--warmup", "2"])
+    a = bench.parse()
+    assert (a.full, a.dump_outputs, a.steps, a.warmup) == (False, None, 4, 2)
+    monkeypatch.setattr(sys, "argv", ["bench.py", "--full", "--dump-outputs", str(tmp_path)])
+    a = bench.parse()
+    assert a.full and a.dump_outputs == str(tmp_path)
+
+    g = torch.Generator().manual_seed(3)
+    mu = torch.randn(2, 1, 72, 72, generator=g, dtype=torch.float64).requires_grad_(True)
+    mu.grad = torch.randn(2, 1, 72, 72, generator=g, dtype=torch.float64)
+    seis = torch.randn(2, 3, 50, 70, generator=g)
+    loss = torch.randn(2, generator=g)
+    monkeypatch.setattr(bench, "DUMP_MAX_ELEMS", 12000)       # seis (21000 elements) is sampled, the rest whole
+    for sub in ("a", "b"):
+        shapes = bench.dump_outputs(str(tmp_path / sub), mu, seis, loss)
+    assert shapes == {"seis": [2, 3, 50, 70], "loss": [2], "grad": [2, 1, 72, 72], "model": [2, 1, 72, 72]}
+    got = {n: np.load(tmp_path / "a" / f"{n}.npy") for n in shapes}
+    assert sorted(os.listdir(tmp_path / "a")) == ["grad.npy", "loss.npy", "model.npy", "seis.npy"]
+    assert all(x.dtype == np.float32 for x in got.values())
+    np.testing.assert_array_equal(got["loss"], loss.numpy())
+    np.testing.assert_array_equal(got["grad"], mu.grad.float().numpy())
+    np.testing.assert_array_equal(got["model"], mu.detach().float().numpy())
+    assert got["seis"].shape == (12000,)
+    idx = np.sort(np.random.default_rng(0).choice(seis.numel(), 12000, replace=False))
+    np.testing.assert_array_equal(got["seis"], seis.numpy().reshape(-1)[idx])
+    np.testing.assert_array_equal(got["seis"], np.load(tmp_path / "b" / "seis.npy"))
+
+
 def test_fallback_restores_each_plans_own_persistent_mode():
     """re-promotion after a persistent fault puts back every plan's own mode.  A plan
     pinned to the chunked kernels stays chunked, a plan pinned to one region class keeps it, and the

@@ -1,7 +1,7 @@
 """Kernel timeline of the configs[1] bench step (bench.py's step(): HIP forward + L1 + TV + adjoint
 + finalize + Adam) from a rocprofv3 rocpd database: per dispatch start offset, duration and the gap
 before it, for the last traced step, and the step's kernel time vs its span.
-Record:  rocprofv3 --kernel-trace -d OUT -o run -- python3 bench.py --steps 6 --warmup 3 --no-loop \
+Record:  rocprofv3 --kernel-trace -d OUT -o run -- python3 bench.py --full --steps 6 --warmup 3 --no-loop \
              --no-red --no-configs4 --no-cpu-baseline
 Print:   python tools/step_timeline.py OUT/.../run_results.db"""
 import sqlite3
