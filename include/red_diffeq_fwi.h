@@ -211,6 +211,44 @@ int rdq_fwi_adjoint(const rdq_fwi_plan *plan, int32_t B, const float *coeffs,
                     const float *history, const float *dseis, float *ring, float *gA,
                     double *gk_part, float *gbeta, hipStream_t stream);
 
+/* Checkpointed gradient: K1 + K2 with the wavefield history bounded by recomputation, for jobs whose
+ * store-all history (rdq_fwi_sizes().history, nt + 2 levels) does not fit.  The first pass keeps two
+ * levels every K steps; the backward walks the segments from the last to the first, recomputes each
+ * one's levels from its checkpoint into `seg` and runs the adjoint over it: 2 (nseg - 1) + K + 2 levels
+ * instead of nt + 2, for one extra forward.
+ *   Layout.  Segments are counted from the END of the record: nseg = ceil(nt / K), boundaries
+ *   b_c = max(nt - c K, 0) for c = 0 .. nseg, segment c = the steps [b_{c+1}, b_c) (the first segment in
+ *   time is the short one).  Checkpoint c, 0 < c < nseg, is the history's slots {b_c, b_c + 1} =
+ *   {P_{b_c - 1}, P_{b_c}}: levels {2 (c - 1), 2 (c - 1) + 1} of `ckpt`, float [nseg - 1][2][B][ns][Hp][ld].
+ *   The boundary at 0 is two zero levels and is not stored.  `seg` is float [K + 2][B][ns][Hp][ld]: while
+ *   segment c is worked on, its level j is the history's slot b_{c+1} + j.  Any K >= 1 is legal (K < 1:
+ *   RDQ_E_INVALID); K >= nt is one segment with no checkpoint (`ckpt` may be NULL) and counts as K = nt.
+ *   Identical results.  Both calls run the chunked kernels (wide or narrow, the plan's depths, chains
+ *   and variant flags) whatever rdq_fwi_set_persistent says.  The recomputed levels are the forward's own
+ *   bits and the adjoint adds into gA / gbeta per launch in the fixed order k = nt .. 1, so seis, gA and
+ *   gbeta are bit-identical to rdq_fwi_forward + rdq_fwi_adjoint on the chunked kernels for every K; each
+ *   gk_part slot receives its launches' fp64 partials in the same k order, but a launch never spans a
+ *   boundary, so gk_part is bit-identical when K is a multiple of the adjoint's depth (then the launches
+ *   are those of the store-all run) and equal to fp64 summation order (~1e-15 relative) otherwise.
+ *   The recompute records no seismograms: `seis` is not needed by rdq_fwi_adjoint_ckpt.  `ring` as for
+ *   rdq_fwi_forward / rdq_fwi_adjoint (one buffer may serve both calls). */
+typedef struct rdq_fwi_ckpt_sizes_t {
+    int32_t nseg; int32_t seg_levels;   /* segments; levels in `seg` (min(K, nt) + 2) */
+    size_t ckpt;                        /* checkpoint store bytes (0 for one segment) */
+    size_t seg;                         /* segment history bytes (<= K+2 levels) */
+} rdq_fwi_ckpt_sizes_t;
+int rdq_fwi_ckpt_sizes(const rdq_fwi_plan *plan, int32_t B, int32_t K, rdq_fwi_ckpt_sizes_t *out);
+/* First pass: seis as rdq_fwi_forward's, and the checkpoint store. */
+int rdq_fwi_forward_ckpt(const rdq_fwi_plan *plan, int32_t B, int32_t K, const float *coeffs,
+                         float *seis, float *ckpt, float *ring, hipStream_t stream);
+/* Backward: the accumulators gA, gk_part, gbeta (overwritten) as rdq_fwi_adjoint's; `seg` is scratch. */
+int rdq_fwi_adjoint_ckpt(const rdq_fwi_plan *plan, int32_t B, int32_t K, const float *coeffs,
+                         const float *ckpt, float *seg, const float *dseis, float *ring,
+                         float *gA, double *gk_part, float *gbeta, hipStream_t stream);
+/* out = {first-pass persistent class (0 = chunked: always, today), nseg, first-pass time-loop launches
+ * per launch chain, backward time-loop launches per chain (every segment's recompute and adjoint)}. */
+int rdq_fwi_ckpt_info(rdq_fwi_plan *plan, int32_t B, int32_t K, int32_t out[4]);
+
 /* K4: d(loss)/d(v) [B][nz][nx] (contiguous) from the accumulators: chain through
  * alpha/beta/sponge(vmin), replicate-pad fold, and (RDQ_VEL_NORMALIZED) the x1500 of the
  * denormalisation. */

@@ -291,6 +291,8 @@ struct FwdTBArgs {
     int n0, nsteps;
     int spw, ns_sh;                      // wide kernels: shots per workgroup, shots of the launch's chain
     float w[FWD_W_MAX];                  // wavelet samples w[n0 .. n0+nsteps-1]
+    int hbase;                           // virtual slot held by hist's first level (0: the whole history;
+                                         // a checkpointed segment's buffer starts at its first boundary)
 };
 
 // exchange two boundary rows each way between the NW waves of the workgroup
@@ -563,12 +565,12 @@ __global__ __launch_bounds__(64 * TB_NW) void k_fwd_tb(FwdTBArgs a)
         }
         const int n = a.n0 + t;
         if (a.hist && xin) {
-            float *HS = a.hist + (size_t)(n + 2) * g.level + so + gx;
+            float *HS = a.hist + (size_t)(n + 2 - a.hbase) * g.level + so + gx;
 #pragma unroll
             for (int r = 0; r < TB_R; ++r)
                 if (rin & (1u << r)) __builtin_nontemporal_store(prv[r], &HS[rofs[r]]);   // streaming
         }
-        if (rrow >= 0 && (rin & (1u << rrow)) && xin && (n % g.st) == 0) {   // pde.py:82-83
+        if (a.seis && rrow >= 0 && (rin & (1u << rrow)) && xin && (n % g.st) == 0) {   // pde.py:82-83 (no seis: a recompute)
             float val = 0.0f;
 #pragma unroll
             for (int r = 0; r < TB_R; ++r) if (r == rrow) val = prv[r];
@@ -606,6 +608,7 @@ struct AdjTBArgs {
     int k0, nsteps, nblk;
     int spw, ns_sh;                      // wide kernels: shots per workgroup, shots of the launch's chain
     float w[ADJ_W_MAX];                  // w[k0-1-t], t < nsteps (narrow: <= TB_MAXT, wide: <= TW_ADJ_MAXT steps)
+    int hbase;                           // virtual slot held by hist's first level (FwdTBArgs::hbase)
 };
 
 // Adjoint with the same register-region blocking, walking k = k0, k0-1, ...:
@@ -673,7 +676,7 @@ __global__ __launch_bounds__(64 * TB_NW, 4) void k_adj_tb(AdjTBArgs a)
     for (int r = 0; r < TB_R; ++r) pofs[r] = (pmask & (1u << r)) ? (rofs[r] + gx) * 4 : OOB;
     const int slice_bytes = (int)(g.slice * 4);
     {
-        const __amdgpu_buffer_rsrc_t HR = rsrc_of(a.hist + (size_t)a.k0 * g.level + so, slice_bytes);
+        const __amdgpu_buffer_rsrc_t HR = rsrc_of(a.hist + (size_t)(a.k0 - a.hbase) * g.level + so, slice_bytes);
 #pragma unroll
         for (int r = 0; r < TB_R; ++r) Pn[r] = bload(HR, pofs[r], 0);   // (not nt: vertically adjacent
     }                                                                          //  tiles re-read halo rows from L2)
@@ -687,7 +690,7 @@ __global__ __launch_bounds__(64 * TB_NW, 4) void k_adj_tb(AdjTBArgs a)
 #pragma unroll
         for (int r = 0; r < TB_R; ++r) P[r] = Pn[r];
         if (t + 1 < a.nsteps) {
-            const __amdgpu_buffer_rsrc_t HR = rsrc_of(a.hist + (size_t)(k - 1) * g.level + so, slice_bytes);
+            const __amdgpu_buffer_rsrc_t HR = rsrc_of(a.hist + (size_t)(k - 1 - a.hbase) * g.level + so, slice_bytes);
 #pragma unroll
             for (int r = 0; r < TB_R; ++r) Pn[r] = bload(HR, pofs[r], 0);
         }
@@ -961,12 +964,12 @@ __global__ __launch_bounds__(64 * NW) void k_fwd_tw(FwdTBArgs a)
         }
         const int n = ka->n0 + t;
         if (ka->hist) {
-            const __amdgpu_buffer_rsrc_t HS = rsrc_of(ka->hist + (size_t)(n + 2) * ka->g.level + soo, sbytes);
+            const __amdgpu_buffer_rsrc_t HS = rsrc_of(ka->hist + (size_t)(n + 2 - ka->hbase) * ka->g.level + soo, sbytes);
 #pragma unroll
             for (int r = 0; r < R; ++r)
                 if (rin & (1u << r)) st2<PAIR, CP_NT>(prv[r], HS, vi0, vi1, rofs[r] * 4);   // streaming
         }
-        if (rrow >= 0 && (rin & (1u << rrow)) && (n % ka->g.st) == 0) {   // pde.py:82-83
+        if (ka->seis && rrow >= 0 && (rin & (1u << rrow)) && (n % ka->g.st) == 0) {   // pde.py:82-83 (no seis: a recompute)
             f32x2 val = prv[0];
 #pragma unroll
             for (int r = 1; r < R; ++r) if (r == rrow) val = prv[r];
@@ -1057,7 +1060,7 @@ __global__ __launch_bounds__(64 * NW) void k_adj_tw(AdjTBArgs a)
         const size_t so_ = (size_t)(b * k_->g.ns + ss_) * k_->g.slice;
         const __amdgpu_buffer_rsrc_t RL1 = rsrc_of(k_->in_l1 + so_, sbytes), RL2 = rsrc_of(k_->in_l2 + so_, sbytes);
         const __amdgpu_buffer_rsrc_t RG = rsrc_of(k_->gA + so_, sbytes);
-        const __amdgpu_buffer_rsrc_t HR = rsrc_of(k_->hist + (size_t)k_->k0 * k_->g.level + so_, sbytes);
+        const __amdgpu_buffer_rsrc_t HR = rsrc_of(k_->hist + (size_t)(k_->k0 - k_->hbase) * k_->g.level + so_, sbytes);
 #pragma unroll
         for (int r = 0; r < R; ++r) L1[r] = ld2<PAIR>(RL1, v0, v1, rofs[r] * 4);   // L_{k+1}
 #pragma unroll
@@ -1091,7 +1094,7 @@ __global__ __launch_bounds__(64 * NW) void k_adj_tw(AdjTBArgs a)
 #pragma unroll
         for (int r = 0; r < R; ++r) P[r] = Pn[r];
         if (t + 1 < T) {   // history P_{k-2} of the next step, on the rows the interior's stencil needs
-            const __amdgpu_buffer_rsrc_t HR = rsrc_of(ka->hist + (size_t)(k - 1) * ka->g.level + soo, sbytes);
+            const __amdgpu_buffer_rsrc_t HR = rsrc_of(ka->hist + (size_t)(k - 1 - ka->hbase) * ka->g.level + soo, sbytes);
 #pragma unroll
             for (int r = 0; r < R; ++r) if (pmask & (1u << r)) Pn[r] = ld2<PAIR>(HR, pv0, pv1, rofs[r] * 4);
         }
@@ -2664,8 +2667,9 @@ __global__ __launch_bounds__(256) void k_smooth_bwd(int kind, int H, int W, cons
 
 // ======================================================================================= plan
 struct GraphEntry {
-    int kind;                 // 0 fwd-history, 1 fwd-ring, 2 adjoint
+    int kind;                 // 0 fwd-history, 1 fwd-ring, 2 adjoint, 3 fwd-checkpoint, 4 adjoint-checkpoint
     int B;
+    int K;                    // checkpoint interval (kinds 3, 4; else 0): it shapes the launch sequence
     const void *ptrs[8];
     hipGraphExec_t exec;
     uint64_t last_use;
@@ -3432,6 +3436,200 @@ int launch_adjoint(rdq_fwi_plan *p, int B, const float *coeffs, const float *his
     return join_chains(p, st, S);
 }
 
+
+// ---- Checkpointed gradient (rdq_fwi_forward_ckpt / rdq_fwi_adjoint_ckpt): the history bounded by
+// recomputation.  Segments of K steps are counted from the END of the record: boundaries b_c =
+// max(nt - c K, 0), c = 0 .. nseg = ceil(nt / K); segment c is the steps [b_{c+1}, b_c), the first one in
+// time being the short one, so the adjoint's launches (k0 = nt, nt - T, ...) are those of a store-all run
+// whenever K is a multiple of its depth.  Checkpoint c (0 < c < nseg) is the two levels {P_{b_c - 1},
+// P_{b_c}} = the history's slots {b_c, b_c + 1}, pair c - 1 of the store; the boundary at 0 is two zero
+// levels, produced by zeroing.
+struct CkptPlan {
+    int K, nseg;
+    int lo(int c) const { return hi(c + 1); }                                   // segment c = steps [lo, hi)
+    int hi(int c) const { return (int)std::max<long long>(nt - (long long)c * K, 0); }
+    int nt;
+};
+CkptPlan ckpt_plan(const rdq_fwi_plan *p, int K)
+{
+    CkptPlan c;
+    c.nt = p->g.nt;
+    c.K = std::min(K, c.nt);
+    c.nseg = (c.nt + c.K - 1) / c.K;
+    return c;
+}
+
+// Levels {0, 1} of a segment buffer from a checkpoint pair (src == nullptr: zeros, the boundary at step
+// 0), for the shots [s_off, s_off + ns_sh) of every model: each launch chain fills its own shots' slices,
+// so the copy needs no ordering against the other chains.  (A kernel, not hipMemcpyAsync: the call is
+// captured into a graph, see zero_regions.)  grid.y = 2 levels x B models.
+__global__ __launch_bounds__(256) void k_ckpt_levels(const float *src, float *dst, size_t level, size_t model,
+                                                     size_t off, size_t run, int B)
+{
+    const int lvl = blockIdx.y / B, b = blockIdx.y - lvl * B;
+    const size_t base = (size_t)lvl * level + (size_t)b * model + off;   // (run <= model - off: inside the level)
+    const size_t stride = (size_t)gridDim.x * blockDim.x;
+    for (size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x; i < run; i += stride)
+        dst[base + i] = src ? src[base + i] : 0.0f;
+}
+
+// First pass of a checkpointed gradient: the no-grad chunked forward (ring ping-pong) with its launches
+// cut at the segment boundaries; the launch that ends on an interior boundary writes its two output
+// levels into the checkpoint store instead of the ring, and the next launch reads them from there (no
+// copy).  Seismograms as rdq_fwi_forward's.
+int launch_forward_ckpt(rdq_fwi_plan *p, int B, int K, const float *coeffs, float *seis, float *ckpt, float *ring,
+                        hipStream_t st)
+{
+    const CkptPlan cp = ckpt_plan(p, K);
+    FwdTBArgs a{};
+    a.g = tb_geo(p, B);
+    const size_t L = a.g.level;
+    const int T = p->wide ? wide_fwd_depth(p) : p->fwd_T, S = chain_count(p), ns = p->g.ns;
+    RDQ_TRY(zero_regions({{ring, 4 * L * sizeof(float)}}, st));   // (no hipMemsetAsync under graph capture)
+    a.coeffs = coeffs;
+    a.cg = coef_gen(p, B, coeffs);
+    a.seis = seis;
+    a.hist = nullptr;
+    RDQ_TRY(fork_chains(p, st, S));
+    for (int c = 0; c < S; ++c) {
+        a.g.s_off = c * ns / S;
+        a.ns_sh = (c + 1) * ns / S - a.g.s_off;
+        const hipStream_t cs = c == 0 ? st : p->aux[c - 1];
+        int i = 0;                                               // ring parity: runs on across segments
+        for (int sg = cp.nseg - 1; sg >= 0; --sg) {
+            const int lo = cp.lo(sg), hi = cp.hi(sg);
+            for (int n0 = lo; n0 < hi; n0 += T, ++i) {
+                a.n0 = n0;
+                a.nsteps = std::min(T, hi - n0);
+                const int Tl = p->wide ? a.nsteps : T;
+                a.g.tiles_x = p->wide ? tw_tiles_x(p->Wp, Tl) : tiles_x(p->Wp, Tl);
+                a.g.ntiles = a.g.tiles_x * (p->wide ? tw_tiles_y(p->Hp, Tl, false) : tiles_y(p->Hp, Tl));
+                a.spw = p->wide ? wide_spw(p->fwd_spw, B * a.g.ntiles, a.ns_sh, false, S) : 1;
+                a.g.ns_grp = (a.ns_sh + a.spw - 1) / a.spw;
+                const dim3 grid((a.g.ntiles + 7) / 8 * 8 * B * a.g.ns_grp);
+                for (int t = 0; t < FWD_W_MAX; ++t) a.w[t] = t < a.nsteps ? p->wavf[n0 + t] : 0.0f;
+                const int pin = i & 1, pout = pin ^ 1;
+                if (n0 == lo && lo > 0) {                        // checkpoint sg + 1 = pair sg
+                    a.in_prev = ckpt + (size_t)(2 * sg) * L;
+                    a.in_cur = ckpt + (size_t)(2 * sg + 1) * L;
+                } else {
+                    a.in_prev = ring + (size_t)(2 * pin) * L;
+                    a.in_cur = ring + (size_t)(2 * pin + 1) * L;
+                }
+                if (n0 + a.nsteps == hi && hi < cp.nt) {         // checkpoint sg = pair sg - 1
+                    a.out_prev = ckpt + (size_t)(2 * (sg - 1)) * L;
+                    a.out_cur = ckpt + (size_t)(2 * (sg - 1) + 1) * L;
+                } else {
+                    a.out_prev = ring + (size_t)(2 * pout) * L;
+                    a.out_cur = ring + (size_t)(2 * pout + 1) * L;
+                }
+                if (p->wide) launch_fwd_w(a.nsteps, p->fwd_gen, (p->Wp & 1) == 0, grid, cs, a);
+                else launch_fwd(T, p->fwd_gen, grid, cs, a);
+            }
+        }
+    }
+    RDQ_CHECK(hipGetLastError());
+    return join_chains(p, st, S);
+}
+
+// Backward of a checkpointed gradient: the segments from the last to the first; each one's levels are
+// recomputed from its checkpoint into `seg` (level j of seg = the history's slot lo + j: the chunked
+// forward's history form with FwdTBArgs::hbase = lo, recording no seismograms), then the chunked adjoint
+// runs over it (AdjTBArgs::hbase = lo; dseis, wavelet and record indices stay absolute).  The adjoint's
+// levels stay in `ring` between launches and its ring parity runs on across segments; ring, gA, gk_part
+// and gbeta are zeroed once.  Every launch of a chain is ordered on the chain's stream, so a segment's
+// recompute overwrites `seg` only after the previous segment's adjoint has read it.
+int launch_adjoint_ckpt(rdq_fwi_plan *p, int B, int K, const float *coeffs, const float *ckpt, float *seg,
+                        const float *dseis, float *ring, float *gA, double *gk, float *gbeta, hipStream_t st)
+{
+    const CkptPlan cp = ckpt_plan(p, K);
+    FwdTBArgs f{};
+    AdjTBArgs a{};
+    f.g = a.g = tb_geo(p, B);
+    const size_t L = a.g.level, slice = a.g.slice;
+    const int Tf = p->wide ? wide_fwd_depth(p) : p->fwd_T, Ta = p->wide ? wide_adj_depth(p) : p->adj_T;
+    const int S = chain_count(p), ns = p->g.ns;
+    const int nblk_alloc = gk_blocks(p);
+    f.coeffs = coeffs; f.cg = coef_gen(p, B, coeffs); f.seis = nullptr; f.hist = seg;
+    f.out_prev = f.out_cur = nullptr;
+    a.coeffs = coeffs; a.hist = seg; a.dseis = dseis; a.gA = gA; a.gk_part = gk; a.gbeta = gbeta;
+    a.cg = f.cg;
+    a.nblk = nblk_alloc;
+    auto geometry = [&](int c, int nsteps) -> unsigned {          // (launch_adjoint's)
+        a.g.s_off = c * ns / S;
+        a.ns_sh = (c + 1) * ns / S - a.g.s_off;
+        const int Tl = p->wide ? nsteps : Ta;
+        a.g.tiles_x = p->wide ? tw_tiles_x(p->Wp, Tl) : tiles_x(p->Wp, Tl);
+        a.g.ntiles = a.g.tiles_x * (p->wide ? tw_tiles_y(p->Hp, Tl, true) : tiles_y(p->Hp, Tl));
+        a.spw = p->wide ? wide_spw(p->adj_spw, B * a.g.ntiles, a.ns_sh, true, S) : 1;
+        a.g.ns_grp = (a.ns_sh + a.spw - 1) / a.spw;
+        return (unsigned)((a.g.ntiles + 7) / 8 * 8 * B * a.g.ns_grp);
+    };
+    {   // the gk_part one-writer invariant, on every adjoint launch of every segment, before anything is enqueued
+        GkWriters writers((size_t)B * ns, nblk_alloc);
+        for (int c = 0; c < S; ++c)
+            for (int sg = 0; sg < cp.nseg; ++sg)
+                for (int k0 = cp.hi(sg); k0 > cp.lo(sg); k0 -= Ta) {
+                    const unsigned grid = geometry(c, std::min(Ta, k0 - cp.lo(sg)));
+                    if (!writers.add(c, grid, a.g.tiles_x, a.g.ntiles, B, ns, a.g.ns_grp, a.g.s_off, a.spw, a.ns_sh))
+                        return RDQ_E_INVALID;
+                }
+    }
+    RDQ_TRY(zero_regions({{ring, 4 * L * sizeof(float)}, {gA, L * sizeof(float)},
+                          {gk, (size_t)B * ns * nblk_alloc * sizeof(double)}, {gbeta, (size_t)B * ns * sizeof(float)}},
+                         st));   // once, before the last segment (no hipMemsetAsync under graph capture)
+    RDQ_TRY(fork_chains(p, st, S));
+    for (int c = 0; c < S; ++c) {
+        const hipStream_t cs = c == 0 ? st : p->aux[c - 1];
+        const int s_off = c * ns / S, ns_sh = (c + 1) * ns / S - s_off;
+        int i = 0;                                               // the adjoint's ring parity
+        for (int sg = 0; sg < cp.nseg; ++sg) {
+            const int lo = cp.lo(sg), hi = cp.hi(sg);
+            {   // slots lo, lo + 1: checkpoint sg + 1 = pair sg, or zeros at the start of the record
+                const size_t run = (size_t)ns_sh * slice;
+                const unsigned gx = (unsigned)std::min<size_t>((run + 255) / 256, 1024);
+                hipLaunchKernelGGL(k_ckpt_levels, dim3(gx, 2 * B), dim3(256), 0, cs,
+                                   lo > 0 ? ckpt + (size_t)(2 * sg) * L : nullptr, seg, L, (size_t)ns * slice,
+                                   (size_t)s_off * slice, run, B);
+            }
+            f.hbase = lo;
+            f.g.s_off = s_off;
+            f.ns_sh = ns_sh;
+            for (int n0 = lo; n0 < hi; n0 += Tf) {               // recompute: slots lo + 2 .. hi + 1
+                f.n0 = n0;
+                f.nsteps = std::min(Tf, hi - n0);
+                const int Tl = p->wide ? f.nsteps : Tf;
+                f.g.tiles_x = p->wide ? tw_tiles_x(p->Wp, Tl) : tiles_x(p->Wp, Tl);
+                f.g.ntiles = f.g.tiles_x * (p->wide ? tw_tiles_y(p->Hp, Tl, false) : tiles_y(p->Hp, Tl));
+                f.spw = p->wide ? wide_spw(p->fwd_spw, B * f.g.ntiles, f.ns_sh, false, S) : 1;
+                f.g.ns_grp = (f.ns_sh + f.spw - 1) / f.spw;
+                const dim3 grid((f.g.ntiles + 7) / 8 * 8 * B * f.g.ns_grp);
+                for (int t = 0; t < FWD_W_MAX; ++t) f.w[t] = t < f.nsteps ? p->wavf[n0 + t] : 0.0f;
+                f.in_prev = seg + (size_t)(n0 - lo) * L;         // slot n0     = P_{n0-1}
+                f.in_cur = seg + (size_t)(n0 - lo + 1) * L;      // slot n0 + 1 = P_{n0}
+                if (p->wide) launch_fwd_w(f.nsteps, p->fwd_gen, (p->Wp & 1) == 0, grid, cs, f);
+                else launch_fwd(Tf, p->fwd_gen, grid, cs, f);
+            }
+            a.hbase = lo;
+            for (int k0 = hi; k0 > lo; k0 -= Ta, ++i) {          // adjoint steps k = hi .. lo + 1: slots lo + 1 .. hi
+                a.k0 = k0;
+                a.nsteps = std::min(Ta, k0 - lo);
+                const dim3 grid(geometry(c, a.nsteps));
+                for (int t = 0; t < ADJ_W_MAX; ++t) a.w[t] = t < a.nsteps ? p->wavf[k0 - 1 - t] : 0.0f;
+                const int pin = i & 1, pout = pin ^ 1;
+                a.in_l1 = ring + (size_t)(2 * pin) * L;
+                a.in_l2 = ring + (size_t)(2 * pin + 1) * L;
+                a.out_l1 = ring + (size_t)(2 * pout) * L;
+                a.out_l2 = ring + (size_t)(2 * pout + 1) * L;
+                if (p->wide) launch_adj_w(a.nsteps, (p->Wp & 1) == 0, !p->adj_tw_fma, grid, cs, a);
+                else launch_adj(Ta, grid, cs, a);
+            }
+        }
+    }
+    RDQ_CHECK(hipGetLastError());
+    return join_chains(p, st, S);
+}
+
 // destroy every cached graph; a graph may still be queued or running (asynchronous launches), so
 // the device is drained first
 void drop_graphs(rdq_fwi_plan *p)
@@ -3443,14 +3641,15 @@ void drop_graphs(rdq_fwi_plan *p)
 }
 
 template <class F>
-int run_cached(rdq_fwi_plan *p, int kind, int B, std::initializer_list<const void *> key, hipStream_t st, F &&launch)
+int run_cached(rdq_fwi_plan *p, int kind, int B, std::initializer_list<const void *> key, hipStream_t st, F &&launch,
+               int K = 0)
 {
     if (!p->graphs) return launch(st);
     const void *k[8] = {nullptr};
     int n = 0;
     for (const void *v : key) k[n++] = v;
     for (auto &e : p->cache)
-        if (e.kind == kind && e.B == B && std::equal(k, k + 8, e.ptrs)) {
+        if (e.kind == kind && e.B == B && e.K == K && std::equal(k, k + 8, e.ptrs)) {
             e.last_use = ++p->tick;
             RDQ_CHECK(hipGraphLaunch(e.exec, st));
             return 0;
@@ -3463,7 +3662,7 @@ int run_cached(rdq_fwi_plan *p, int kind, int B, std::initializer_list<const voi
     if (rc) { if (graph) (void)hipGraphDestroy(graph); return rc; }
     RDQ_CHECK(ee);
     GraphEntry e{};
-    e.kind = kind; e.B = B;
+    e.kind = kind; e.B = B; e.K = K;
     std::copy(k, k + 8, e.ptrs);
     const hipError_t ie = hipGraphInstantiate(&e.exec, graph, nullptr, nullptr, 0);
     (void)hipGraphDestroy(graph);
@@ -3911,6 +4110,72 @@ int rdq_fwi_adjoint(const rdq_fwi_plan *pc, int32_t B, const float *coeffs, cons
     return run_cached(p, 2, B, {coeffs, hist, dseis, ring, gA, gk, gbeta}, st, [&](hipStream_t s) {
         return launch_adjoint(p, B, coeffs, hist, dseis, ring, gA, gk, gbeta, s);
     });
+}
+
+int rdq_fwi_ckpt_sizes(const rdq_fwi_plan *p, int32_t B, int32_t K, rdq_fwi_ckpt_sizes_t *o)
+{
+    if (!p || !o || B < 1 || K < 1) return RDQ_E_INVALID;
+    const CkptPlan cp = ckpt_plan(p, K);
+    const size_t level = (size_t)B * p->g.ns * p->Hp * p->ld * sizeof(float);
+    o->nseg = cp.nseg;
+    o->seg_levels = cp.K + 2;
+    o->ckpt = 2 * (size_t)(cp.nseg - 1) * level;
+    o->seg = (size_t)(cp.K + 2) * level;
+    return 0;
+}
+
+int rdq_fwi_ckpt_info(rdq_fwi_plan *p, int32_t B, int32_t K, int32_t out[4])
+{
+    if (!p || !out || B < 1 || K < 1) return RDQ_E_INVALID;
+    std::lock_guard<std::mutex> lk(p->mu);
+    const CkptPlan cp = ckpt_plan(p, K);
+    const int Tf = p->wide ? wide_fwd_depth(p) : p->fwd_T, Ta = p->wide ? wide_adj_depth(p) : p->adj_T;
+    int nf = 0, na = 0;
+    for (int sg = 0; sg < cp.nseg; ++sg) {
+        const int len = cp.hi(sg) - cp.lo(sg);
+        nf += (len + Tf - 1) / Tf;
+        na += (len + Ta - 1) / Ta;
+    }
+    out[0] = 0;            // the first pass runs the chunked kernels
+    out[1] = cp.nseg;
+    out[2] = nf;
+    out[3] = nf + na;      // every segment: its recompute, then its adjoint
+    return 0;
+}
+
+int rdq_fwi_forward_ckpt(const rdq_fwi_plan *pc, int32_t B, int32_t K, const float *coeffs, float *seis,
+                         float *ckpt, float *ring, hipStream_t st)
+{
+    rdq_fwi_plan *p = const_cast<rdq_fwi_plan *>(pc);
+    if (!p || !coeffs || !seis || !ring || B < 1 || K < 1) return RDQ_E_INVALID;
+    if (!ckpt && ckpt_plan(p, K).nseg > 1) return RDQ_E_INVALID;
+    std::lock_guard<std::mutex> lk(p->mu);
+    RDQ_TRY(plan_enter(p, st));
+    return run_cached(p, 3, B, {coeffs, seis, ckpt, ring}, st,
+                      [&](hipStream_t s) { return launch_forward_ckpt(p, B, K, coeffs, seis, ckpt, ring, s); },
+                      ckpt_plan(p, K).K);
+}
+
+int rdq_fwi_adjoint_ckpt(const rdq_fwi_plan *pc, int32_t B, int32_t K, const float *coeffs, const float *ckpt,
+                         float *seg, const float *dseis, float *ring, float *gA, double *gk, float *gbeta,
+                         hipStream_t st)
+{
+    rdq_fwi_plan *p = const_cast<rdq_fwi_plan *>(pc);
+    if (!p || !coeffs || !seg || !dseis || !ring || !gA || !gk || !gbeta || B < 1 || K < 1) return RDQ_E_INVALID;
+    if (!ckpt && ckpt_plan(p, K).nseg > 1) return RDQ_E_INVALID;
+    std::lock_guard<std::mutex> lk(p->mu);
+    RDQ_TRY(plan_enter(p, st));
+    if (p->rmulti) {   // several receivers in a column: fold the residuals per column (ring tail), as rdq_fwi_adjoint
+        float *fold = ring + 8 * (size_t)B * p->g.ns * p->Hp * p->ld;
+        const size_t rows = (size_t)B * p->g.ns * p->nrec, n = rows * p->ncolr;
+        hipLaunchKernelGGL(k_rcv_fold, dim3((unsigned)std::min<size_t>((n + 255) / 256, 4096)), dim3(256), 0, st,
+                           dseis, fold, p->d_colx, p->d_rcv_start, p->d_rcv_list, p->g.ng, p->ncolr, rows);
+        RDQ_CHECK(hipGetLastError());
+        dseis = fold;
+    }
+    return run_cached(p, 4, B, {coeffs, ckpt, seg, dseis, ring, gA, gk, gbeta}, st, [&](hipStream_t s) {
+        return launch_adjoint_ckpt(p, B, K, coeffs, ckpt, seg, dseis, ring, gA, gk, gbeta, s);
+    }, ckpt_plan(p, K).K);
 }
 
 int rdq_fwi_grad_finalize(const rdq_fwi_plan *p, int32_t B, const float *coeffs, const void *vstat,

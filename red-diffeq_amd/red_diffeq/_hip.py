@@ -34,6 +34,11 @@ class FwiSizes(ctypes.Structure):
                 ("colsum", c_size_t)]
 
 
+class FwiCkptSizes(ctypes.Structure):
+    """struct rdq_fwi_ckpt_sizes_t."""
+    _fields_ = [("nseg", c_int32), ("seg_levels", c_int32), ("ckpt", c_size_t), ("seg", c_size_t)]
+
+
 class ConvDesc(ctypes.Structure):
     """struct rdq_conv_desc."""
     _fields_ = [(n, c_int32) for n in ("B", "cin1", "cin2", "H", "W", "cout", "kh", "kw", "pad", "in_mode")]
@@ -67,6 +72,11 @@ SIGNATURES = {
     "rdq_fwi_forward": (c_int32, [c_void_p, c_int32, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p]),
     "rdq_fwi_adjoint": (c_int32, [c_void_p, c_int32, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p,
                                   c_void_p, c_void_p, c_void_p]),
+    "rdq_fwi_ckpt_sizes": (c_int32, [c_void_p, c_int32, c_int32, ctypes.POINTER(FwiCkptSizes)]),
+    "rdq_fwi_forward_ckpt": (c_int32, [c_void_p, c_int32, c_int32, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p]),
+    "rdq_fwi_adjoint_ckpt": (c_int32, [c_void_p, c_int32, c_int32, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p,
+                                       c_void_p, c_void_p, c_void_p, c_void_p]),
+    "rdq_fwi_ckpt_info": (c_int32, [c_void_p, c_int32, c_int32, ctypes.POINTER(c_int32)]),
     "rdq_fwi_grad_finalize": (c_int32, [c_void_p, c_int32, c_void_p, c_void_p, c_void_p, c_void_p,
                                         c_void_p, c_int32, c_void_p, c_void_p, c_void_p]),
     "rdq_l1_partial_bytes": (c_size_t, [c_int32, c_int64]),

@@ -14,6 +14,11 @@ torch.compile see them as ordinary operators instead of opaque ctypes calls.
     red_diffeq::fwi_grad_finalize(coeffs, vstat, gA, gk, gbeta, plan, B, vel_mode) -> grad   K4
     red_diffeq::fwi(v, plan, vel_mode, keep_history) -> (seis, coeffs, vstat, history)
         differentiable in v (register_autograd: adjoint + finalize), what FWIForward calls
+    red_diffeq::fwi_forward_ckpt(coeffs, plan, B, K) -> (seis, ckpt)               K1, checkpoints every K steps
+    red_diffeq::fwi_adjoint_ckpt(coeffs, ckpt, seg, dseis, plan, B, K) -> (gA, gk, gbeta)
+        K2 over segments recomputed into the scratch `seg` (the one mutated argument)
+    red_diffeq::fwi_ckpt(v, plan, vel_mode, K) -> (seis, coeffs, vstat, ckpt)
+        differentiable in v with the history bounded by recomputation (FWIForward(checkpoint=...))
   U-Net (include/red_diffeq_unet.h)
     conv2d_mfma, conv2d_rms, conv2d_gn_silu, conv2d_bf16_gn_silu, conv2d_bf16_gn_silu_out, conv2d_gn_silu_sc, conv2d_gn_silu_lsm, conv2d_gn_silu_out, unet_head,
     gn_silu, rmsnorm, linear, time_mlp, linear_silu_multi, sinusoidal_emb, linear_attn, linear_attn_block, attn,
@@ -202,6 +207,97 @@ def _fwi_backward(ctx, gseis, _gc, _gv, _gh):
 
 
 fwi.register_autograd(_fwi_backward, setup_context=_fwi_setup)
+
+
+# ---- checkpointed gradient: the history bounded by recomputation (rdq_fwi_forward_ckpt / _adjoint_ckpt)
+@torch.library.custom_op(f"{LIB}::fwi_forward_ckpt", mutates_args=())
+def fwi_forward_ckpt(coeffs: Tensor, plan: int, B: int, K: int) -> Tuple[Tensor, Tensor]:
+    """First pass: (seis, ckpt), ckpt = two wavefield levels per interior segment boundary."""
+    p = _plan(plan)
+    _hip.require_device(coeffs)
+    cs = p.ckpt_sizes(B, K)                      # (K < 1 raises here)
+    seis = torch.empty(_seis_shape(p, B), dtype=torch.float32, device=coeffs.device)
+    ckpt = _f32(cs.ckpt, coeffs.device)
+    ring = _f32(p.sizes(B).ring, coeffs.device)
+    _hip.check(p.lib.rdq_fwi_forward_ckpt(p.handle, B, K, _hip.ptr(coeffs), _hip.ptr(seis), _hip.ptr(ckpt),
+                                          _hip.ptr(ring), _hip.stream_of(coeffs)), "rdq_fwi_forward_ckpt")
+    return seis, ckpt
+
+
+@fwi_forward_ckpt.register_fake
+def _(coeffs, plan, B, K):
+    p = _plan(plan)
+    return coeffs.new_empty(_seis_shape(p, B)), coeffs.new_empty(int(p.ckpt_sizes(B, K).ckpt) // 4)
+
+
+@torch.library.custom_op(f"{LIB}::fwi_adjoint_ckpt", mutates_args=("seg",))
+def fwi_adjoint_ckpt(coeffs: Tensor, ckpt: Tensor, seg: Tensor, dseis: Tensor, plan: int, B: int,
+                     K: int) -> Tuple[Tensor, Tensor, Tensor]:
+    """Backward: every segment recomputed into the scratch `seg`, then its adjoint; (gA, gk, gbeta)."""
+    p = _plan(plan)
+    _hip.require_device(coeffs, ckpt, seg, dseis)
+    sz, cs = p.sizes(B), p.ckpt_sizes(B, K)
+    if dseis.shape != _seis_shape(p, B):
+        raise ValueError("fwi_adjoint_ckpt: dseis does not match the plan")
+    if ckpt.dtype != torch.float32 or seg.dtype != torch.float32 or ckpt.numel() * 4 != cs.ckpt \
+            or seg.numel() * 4 != cs.seg or not ckpt.is_contiguous() or not seg.is_contiguous():
+        raise ValueError(f"fwi_adjoint_ckpt: ckpt / seg must be contiguous fp32 of {cs.ckpt} / {cs.seg} bytes "
+                         f"(K = {K}), got {ckpt.numel() * ckpt.element_size()} / {seg.numel() * seg.element_size()}")
+    dseis = dseis.float().contiguous()
+    ring = _f32(sz.ring, coeffs.device)
+    gA = _f32(sz.gA, coeffs.device)
+    gk = torch.empty(int(sz.gk_part) // 8, dtype=torch.float64, device=coeffs.device)
+    gb = _f32(sz.gbeta, coeffs.device)
+    _hip.check(p.lib.rdq_fwi_adjoint_ckpt(p.handle, B, K, _hip.ptr(coeffs), _hip.ptr(ckpt), _hip.ptr(seg),
+                                          _hip.ptr(dseis), _hip.ptr(ring), _hip.ptr(gA), _hip.ptr(gk), _hip.ptr(gb),
+                                          _hip.stream_of(coeffs)), "rdq_fwi_adjoint_ckpt")
+    return gA, gk, gb
+
+
+@fwi_adjoint_ckpt.register_fake
+def _(coeffs, ckpt, seg, dseis, plan, B, K):
+    sz = _plan(plan).sizes(B)
+    return (coeffs.new_empty(int(sz.gA) // 4), coeffs.new_empty(int(sz.gk_part) // 8, dtype=torch.float64),
+            coeffs.new_empty(int(sz.gbeta) // 4))
+
+
+@torch.library.custom_op(f"{LIB}::fwi_ckpt", mutates_args=())
+def fwi_ckpt(v: Tensor, plan: int, vel_mode: int, K: int) -> Tuple[Tensor, Tensor, Tensor, Tensor]:
+    """seis = FWM(v) (K3 + the checkpointed first pass); coeffs / vstat / ckpt are returned for the backward."""
+    coeffs, vstat = fwi_coeffs(v, plan, vel_mode)
+    seis, ckpt = fwi_forward_ckpt(coeffs, plan, v.shape[0], K)
+    return seis, coeffs, vstat, ckpt
+
+
+@fwi_ckpt.register_fake
+def _(v, plan, vel_mode, K):
+    coeffs, vstat = _fake_coeffs(v, plan)
+    p = _plan(plan)
+    B = v.shape[0]
+    return (coeffs.new_empty(_seis_shape(p, B)), coeffs, vstat,
+            coeffs.new_empty(int(p.ckpt_sizes(B, K).ckpt) // 4))
+
+
+def _fwi_ckpt_setup(ctx, inputs, output):
+    v, plan, vel_mode, K = inputs
+    _, coeffs, vstat, ckpt = output
+    ctx.mark_non_differentiable(coeffs, vstat, ckpt)
+    ctx.set_materialize_grads(False)
+    ctx.plan, ctx.vel_mode, ctx.B, ctx.K = plan, vel_mode, v.shape[0], K
+    ctx.coeffs, ctx.vstat, ctx.ckpt = coeffs, vstat, ckpt
+
+
+def _fwi_ckpt_backward(ctx, gseis, _gc, _gv, _gk):
+    p = _plan(ctx.plan)
+    seg = _f32(p.ckpt_sizes(ctx.B, ctx.K).seg, ctx.coeffs.device)
+    gA, gk, gb = fwi_adjoint_ckpt(ctx.coeffs, ctx.ckpt, seg, gseis.contiguous(), ctx.plan, ctx.B, ctx.K)
+    ctx.ckpt = None                     # the two history buffers: released as soon as the adjoint has run
+    del seg
+    g = fwi_grad_finalize(ctx.coeffs, ctx.vstat, gA, gk, gb, ctx.plan, ctx.B, ctx.vel_mode)
+    return g, None, None, None
+
+
+fwi_ckpt.register_autograd(_fwi_ckpt_backward, setup_context=_fwi_ckpt_setup)
 
 
 # ---------------------------------------------------------------------------------------- U-Net

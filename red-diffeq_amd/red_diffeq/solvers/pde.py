@@ -232,12 +232,72 @@ class FwiPlan:
     def finalize(self, coeffs, vstat, gA, gk, gb, B, vel_mode):
         return torch.ops.red_diffeq.fwi_grad_finalize(coeffs, vstat, gA, gk, gb, self.op_id, B, vel_mode)
 
+    # ---- checkpointed gradient (rdq_fwi_*_ckpt): history bounded by recomputation ----
+    def ckpt_sizes(self, B, K):
+        """rdq_fwi_ckpt_sizes_t of a checkpointed gradient with K steps per segment: .nseg, .seg_levels,
+        .ckpt / .seg bytes."""
+        key = ("ckpt", int(B), int(K))
+        if key not in self._sizes:
+            s = _hip.FwiCkptSizes()
+            _hip.check(self.lib.rdq_fwi_ckpt_sizes(self.handle, int(B), int(K), ctypes.byref(s)), "rdq_fwi_ckpt_sizes")
+            self._sizes[key] = s
+        return self._sizes[key]
+
+    def ckpt_info(self, B, K):
+        """{'fwd_class' (first-pass persistent class, 0 = chunked), 'nseg', 'fwd_launches', 'bwd_launches'}
+        (time-loop launches per launch chain; the backward's are every segment's recompute + adjoint)."""
+        out = (ctypes.c_int32 * 4)()
+        _hip.check(self.lib.rdq_fwi_ckpt_info(self.handle, int(B), int(K), out), "rdq_fwi_ckpt_info")
+        return {"fwd_class": int(out[0]), "nseg": int(out[1]), "fwd_launches": int(out[2]),
+                "bwd_launches": int(out[3])}
+
+    def forward_ckpt(self, coeffs, B, K):
+        """First pass: (seis, ckpt)."""
+        return torch.ops.red_diffeq.fwi_forward_ckpt(coeffs, self.op_id, int(B), int(K))
+
+    def adjoint_ckpt(self, coeffs, ckpt, dseis, B, K):
+        """Backward over the recomputed segments: (gA, gk, gbeta); the segment buffer lives for the call."""
+        seg = torch.empty(int(self.ckpt_sizes(B, K).seg) // 4, dtype=torch.float32, device=coeffs.device)
+        return torch.ops.red_diffeq.fwi_adjoint_ckpt(coeffs, ckpt, seg, dseis, self.op_id, int(B), int(K))
+
+
+def checkpoint_levels(nt, K):
+    """Wavefield levels a checkpointed gradient with K steps per segment holds (include/red_diffeq_fwi.h):
+    two per interior segment boundary, plus the segment buffer of min(K, nt) + 2."""
+    K = min(int(K), int(nt))
+    nseg = -(-int(nt) // K)
+    return 2 * (nseg - 1) + K + 2
+
+
+def choose_checkpoint(nt, level_bytes, budget_bytes):
+    """History policy under a byte budget: None = store-all (its nt + 2 levels fit), else the LARGEST K
+    whose checkpoint store + segment buffer fit (fewest segments = fewest short tail launches; the
+    recompute costs one forward whatever K is).  ValueError when even the smallest footprint (K near
+    sqrt(2 nt)) does not fit."""
+    nt, level_bytes = int(nt), int(level_bytes)
+    if nt < 1 or level_bytes < 1:
+        raise ValueError("choose_checkpoint: nt and level_bytes must be positive")
+    if (nt + 2) * level_bytes <= budget_bytes:
+        return None
+    for K in range(nt, 0, -1):
+        if checkpoint_levels(nt, K) * level_bytes <= budget_bytes:
+            return K
+    need = min(checkpoint_levels(nt, K) for K in range(1, nt + 1)) * level_bytes
+    raise ValueError(f"history budget of {int(budget_bytes)} bytes is too small: the smallest checkpointed "
+                     f"history needs {need} bytes (store-all: {(nt + 2) * level_bytes})")
+
 
 class FWIForward(nn.Module):
     """Drop-in for red_diffeq.solvers.pde.FWIForward (pde.py:6-93)."""
 
     def __init__(self, ctx, device, sample_temporal=1, sample_spatial=1.0, normalize=True,
-                 v_denorm_func=None, s_norm_func=None, shots=None):
+                 v_denorm_func=None, s_norm_func=None, shots=None, checkpoint=None, history_budget_gb=None):
+        """checkpoint / history_budget_gb (also read from ``ctx`` when the keyword is None, so a YAML's
+        ``pde:`` section can set them): None / None = the store-all history, today's path; checkpoint = K
+        (int >= 1) = a checkpointed gradient with K steps per segment (two wavefield levels kept every K
+        steps, each segment recomputed in the backward: 2 nt / K + K levels instead of nt + 2, one extra
+        forward); checkpoint = "auto", or a budget alone = store-all while its history fits
+        history_budget_gb (GiB), else the largest K that fits (choose_checkpoint)."""
         super().__init__()
         self.device = device
         self.normalize = normalize
@@ -254,6 +314,17 @@ class FWIForward(nn.Module):
         else:
             ctx["gx"] = np.array(ctx["gx"]) * ctx["dx"]
         self.ctx = ctx
+        self.checkpoint = checkpoint if checkpoint is not None else ctx.get("checkpoint")
+        self.history_budget_gb = history_budget_gb if history_budget_gb is not None else ctx.get("history_budget_gb")
+        if isinstance(self.checkpoint, str):
+            if self.checkpoint != "auto":
+                raise ValueError(f"checkpoint must be None, an int >= 1 or 'auto', got {self.checkpoint!r}")
+            if self.history_budget_gb is None:
+                raise ValueError("checkpoint='auto' needs history_budget_gb")
+        elif self.checkpoint is not None:
+            self.checkpoint = int(self.checkpoint)
+            if self.checkpoint < 1:
+                raise ValueError(f"checkpoint must be >= 1, got {self.checkpoint}")
         # shot-parallel sharding: this operator models only shots[start:stop]
         self.shots = (0, len(ctx["sx"])) if shots is None else (int(shots[0]), int(shots[1]))
         self.shots_explicit = shots is not None
@@ -328,8 +399,22 @@ class FWIForward(nn.Module):
         plan = self._plan(v.shape[2], v.shape[3], v.device)
         self._last = plan
         keep = bool(v.requires_grad and torch.is_grad_enabled())
-        s = torch.ops.red_diffeq.fwi(v, plan.op_id, vel_mode, keep)[0]   # backward: K2 + K4 (ops.py)
+        K = self.checkpoint_interval(plan, v.shape[0]) if keep else None
+        if K is not None:   # history bounded by recomputation; backward: recompute + K2 per segment, K4
+            s = torch.ops.red_diffeq.fwi_ckpt(v, plan.op_id, vel_mode, K)[0]
+        else:
+            s = torch.ops.red_diffeq.fwi(v, plan.op_id, vel_mode, keep)[0]   # backward: K2 + K4 (ops.py)
         return self.s_norm_func(s) if self.normalize else s
+
+    def checkpoint_interval(self, plan, B):
+        """Steps per segment of the checkpointed gradient a differentiable call with batch B runs, or None
+        for the store-all history (see __init__)."""
+        if isinstance(self.checkpoint, int):
+            return self.checkpoint
+        if self.history_budget_gb is None:
+            return None
+        sz = plan.sizes(B)
+        return choose_checkpoint(plan.nt, sz.history // (plan.nt + 2), int(float(self.history_budget_gb) * 2 ** 30))
 
     def check(self):
         """Raise if a persistent kernel's neighbour hand-off timed out since the last check
