@@ -2052,7 +2052,7 @@ __global__ __launch_bounds__(64 * NW) void k_adj_pt(AdjPtArgs a)
         const int so_ = (SOFF);                                                                     \
         _Pragma("unroll") for (int i = 0; i < RP; ++i) {                                             \
             PD[i].x = bload_nt(HR, pr[i], so_);                                                     \
-            PD[i].y = bload_nt(HR, pr[PT_MIR ? R - 1 - i : i + RP], so_);                           \
+            PD[i].y = bload_nt(HR, pr[R - 1 - i], so_);   /* mirrored pairs {i, R-1-i} */          \
         }                                                                                           \
     }
 
@@ -2091,44 +2091,14 @@ __global__ __launch_bounds__(64 * NW) void k_adj_pt(AdjPtArgs a)
         }                                                                                           \
     }
 
-// one adjoint step k: CUR = L_{k+1}, PRV = L_{k+2} -> L_k; window P0 / P1 / P2 as ADJR_GRAD;
-// history slot k-2 (the next step's P_{k-3}) prefetched into PN.  (Moving the gradient's history
-// half between the barrier and the halo reads' use, as the forward does with its halo-free work,
-// needs 8 more VGPRs than the 168 that 3 waves / SIMD allow: it spilled and ran 2.6x slower.)
-#define ADJR_STEP(CUR, PRV, P0, P1, P2, PN)                                                         \
-    {                                                                                               \
-        if (grad && k >= 2) ADJR_LOAD(PN, HRe, (T - 1 - t) * L4)                                    \
-        const float dcur = dv[t];                                                                   \
-        f32x2 q[RP];                                                                                \
-        _Pragma("unroll") for (int i = 0; i < RP; ++i) q[i] = A[i] * CUR[i];                         \
-        const Halo4 h4 = exchange_nw<NW>(xch, j & 1, w, lane, q[0].x, q[1].x, q[RP - 2].y, q[RP - 1].y); \
-        const f32x2 eU1 = {h4.u1, q[RP - 1].x}, eU2 = {h4.u2, q[RP - 2].x};                         \
-        const f32x2 eD1 = {q[0].y, h4.d1}, eD2 = {q[1].y, h4.d2};                                   \
-        _Pragma("unroll") for (int i = 0; i < RP; ++i) {                                             \
-            PAIR_VERT(q, i, m1, p1, m2, p2)                                                         \
-            const f32x2 c = q[i];                                                                   \
-            const f32x2 xl1 = {dpp_shr1(c.x), dpp_shr1(c.y)}, xr1 = {dpp_shl1(c.x), dpp_shl1(c.y)}; \
-            f32x2 n1 = m1 + p1; n1 = n1 + xl1; n1 = n1 + xr1;                                       \
-            f32x2 n2 = m2 + p2;                        /* x -+ 2 taps: fused v_add_f32_dpp */       \
-            n2.x = n2.x + dpp_shr1(xl1.x); n2.y = n2.y + dpp_shr1(xl1.y);                           \
-            n2.x = n2.x + dpp_shl1(xr1.x); n2.y = n2.y + dpp_shl1(xr1.y);                           \
-            const f32x2 nb = fma2(kC3, n2, kC2 * n1);                                               \
-            PRV[i] = fma2(T1v[i], CUR[i], fma2(-T2v[i], PRV[i], nb));                               \
-        }                                                                                           \
-        if (rrow >= 0 && rec_index(k - 1, g.st) >= 0) {   /* uniform: the receiver row's wave */    \
-            int rp_ = rpair;                                 /* one packed add on the row's pair */  \
-            LAUNDER(rp_);                                                                           \
-            const f32x2 dv_ = rhalf ? f32x2{-0.0f, dcur} : f32x2{dcur, -0.0f};   /* -0: no-op */     \
-            _Pragma("unroll") for (int i = 0; i < RP; ++i) if (i == rp_) PRV[i] = PRV[i] + dv_;      \
-        }                                                                                           \
-        if (t + 1 < T || last) ADJR_GRAD(CUR, PRV, wv[t], P0, P1, P2)                               \
-    }
-
-// Barrier-free adjoint step (mirrored pairs, the forward's LDS mailbox xm_*): the wave waits
-// only for its two neighbours' A L_{k+1} boundary rows, computes its two boundary pairs (receiver
-// residual included), publishes their A L_k rows for the next step, then its interior pair.  Per row
-// the operations and their order are ADJR_STEP's (m1 + p1 commutes: same bits).  (The gradient's
-// history half ahead of the wait, as the forward's time terms, needs 6 more VGPRs: 84 B/lane scratch.)
+// One adjoint step k: CUR = L_{k+1}, PRV = L_{k+2} -> L_k; window P0 / P1 / P2 as ADJR_GRAD; history
+// slot k-2 (the next step's P_{k-3}) prefetched into PN.  Barrier-free (mirrored pairs, the forward's
+// LDS mailbox xm_*): the wave waits only for its two neighbours' A L_{k+1} boundary rows, computes its
+// two boundary pairs (receiver residual included), publishes their A L_k rows for the next step, then
+// its interior pair.  Per row the operations and their order are those of the barrier-synchronised step
+// it replaced in round 6 (m1 + p1 commutes: same bits; 1.646 -> 1.577 ms at configs[1],
+// profiles/r6/adj_nb_ab.txt).  (The gradient's history half ahead of the wait, as the forward's time
+// terms, needs 6 more VGPRs: 84 B/lane scratch.)
 #define ADJR_PAIRS_NB(CUR, PRV, LO, HI)                                                             \
     {                                                                                               \
         _Pragma("unroll") for (int i = (LO); i < (HI); ++i) {                                        \
@@ -2172,13 +2142,13 @@ template <int T, int NW, int RW, bool PROF>
 __global__ __launch_bounds__(64 * NW) void k_adj_pr(AdjPtArgs a)
 {
     unsigned long long *const prof = PROF ? a.prof : nullptr;   // phase counters: profiled build only
-    constexpr bool ADJ_NB = true;                         // barrier-free steps (ADJR_STEP_NB): 1.646 ->
-                                                          // 1.577 ms at configs[1] (profiles/r6/adj_nb_ab.txt)
-    constexpr bool PT_PRIO = ADJ_NB;                      // wave priorities (PT_PRIO_*)
-    constexpr bool PT_MIR = ADJ_NB;                       // mirrored pairs for the exchange's boundary rows
-    __shared__ float xch[2][NW][4][64];                   // (the unused exchange is not allocated)
+    constexpr bool PT_PRIO = true;                        // wave priorities (PT_PRIO_*)
+    constexpr bool PT_MIR = true;                         // mirrored pairs for the exchange's boundary rows
     __shared__ XmBox<NW> xm;                              // the waves' inboxes (xm_*)
     __shared__ double red[64 * NW];
+    // the LDS the residency decision (resident_capacity) depends on: the mailboxes and the reduction
+    static_assert(sizeof(XmBox<NW>) + sizeof(double) * 64 * NW == (size_t)NW * 4608 && NW <= 16,
+                  "k_adj_pr: 4 KB of mailboxes + 512 B of reduction per wave (72 KB at 16 waves)");
     const TBGeo &g = a.g;
     PT_REGION_INIT(NW, RW)
     const float *AL = a.coeffs + (size_t)b * g.slice;
@@ -2202,9 +2172,9 @@ __global__ __launch_bounds__(64 * NW) void k_adj_pr(AdjPtArgs a)
     const float *DSb = a.dseis + (size_t)bs * g.nrec * g.dstride;
     const __amdgpu_buffer_rsrc_t DSR = rsrc_of(DSb);
     // source / receiver rows as (row pair, half): a step touches one pair, not all eight rows
-    const int spair = __builtin_amdgcn_readfirstlane(srow < 0 ? 0 : PT_MIR ? (srow < RP ? srow : R - 1 - srow) : srow % RP);
-    const int rpair = __builtin_amdgcn_readfirstlane(rrow < 0 ? 0 : PT_MIR ? (rrow < RP ? rrow : R - 1 - rrow) : rrow % RP);
-    const bool shalf = srow >= RP, rhalf = rrow >= RP;   // the half is r >= RP in both pairings
+    const int spair = __builtin_amdgcn_readfirstlane(srow < 0 ? 0 : srow < RP ? srow : R - 1 - srow);
+    const int rpair = __builtin_amdgcn_readfirstlane(rrow < 0 ? 0 : rrow < RP ? rrow : R - 1 - rrow);
+    const bool shalf = srow >= RP, rhalf = rrow >= RP;   // the half is r >= RP
     // the receiver's row pair among the boundary pairs 0, 1 (rlo) or the interior ones (rhi): wave-uniform
     const int rlo = __builtin_amdgcn_readfirstlane(rrow >= 0 && rpair < 2 ? 1 : 0);
     const int rhi = __builtin_amdgcn_readfirstlane(rrow >= 0 && rpair >= 2 ? 1 : 0);
@@ -2256,12 +2226,9 @@ __global__ __launch_bounds__(64 * NW) void k_adj_pr(AdjPtArgs a)
     bool live = true;
     unsigned long long tsw = 0, tst = 0, tpb = 0, tm = prof ? __builtin_amdgcn_s_memrealtime() : 0;
     unsigned long long tfp = 0, npass = 0;                // profile: first-pass latency, sweep passes
-    if constexpr (ADJ_NB) {
-        xm_init<NW>(xm, w, lane);                         // no flag matches a tag until written
-        __syncthreads();
-        xm_put<NW>(xm, 0, w, lane, 1u, f32x2{0.0f, 0.0f}, f32x2{0.0f, 0.0f});   // A L_{nt+1} = 0, step 0's tag
-    }
-#define ADJR_STEP_SEL(...) { if constexpr (ADJ_NB) ADJR_STEP_NB(__VA_ARGS__) else ADJR_STEP(__VA_ARGS__) }
+    xm_init<NW>(xm, w, lane);                             // no flag matches a tag until written
+    __syncthreads();
+    xm_put<NW>(xm, 0, w, lane, 1u, f32x2{0.0f, 0.0f}, f32x2{0.0f, 0.0f});   // A L_{nt+1} = 0, step 0's tag
     for (int e = 0; e < nep; ++e) {
         const int ke = a.nt - e * T;                      // first step k of this epoch
         const bool last = e + 1 == nep;
@@ -2275,10 +2242,10 @@ __global__ __launch_bounds__(64 * NW) void k_adj_pr(AdjPtArgs a)
             const int j = e * T + t;
             if (j >= a.nt) break;
             const int k = ke - t;
-            if ((t & 3) == 0) ADJR_STEP_SEL(L1, L0, Q0, Q1, Q2, Q3)
-            else if ((t & 3) == 1) ADJR_STEP_SEL(L0, L1, Q1, Q2, Q3, Q0)
-            else if ((t & 3) == 2) ADJR_STEP_SEL(L1, L0, Q2, Q3, Q0, Q1)
-            else ADJR_STEP_SEL(L0, L1, Q3, Q0, Q1, Q2)
+            if ((t & 3) == 0) ADJR_STEP_NB(L1, L0, Q0, Q1, Q2, Q3)
+            else if ((t & 3) == 1) ADJR_STEP_NB(L0, L1, Q1, Q2, Q3, Q0)
+            else if ((t & 3) == 2) ADJR_STEP_NB(L1, L0, Q2, Q3, Q0, Q1)
+            else ADJR_STEP_NB(L0, L1, Q3, Q0, Q1, Q2)
         }
         if (T & 1) {   // keep "L1 = newest" at every epoch boundary
 #pragma unroll
@@ -2296,8 +2263,8 @@ __global__ __launch_bounds__(64 * NW) void k_adj_pr(AdjPtArgs a)
             PT_PROF(tpb)
             PT_SWEEP_DELAY()
             PT_SWEEP(GR, tag, L0, L1, PT_ADJ_SG)
-            if constexpr (ADJ_NB)   // the next step's boundary rows, with the halo cells the sweep reloaded
-                xm_put<NW>(xm, (e + 1) * T & 1, w, lane, (unsigned)((e + 1) * T) + 1u, A[0] * L1[0], A[1] * L1[1]);
+            // the next step's boundary rows, with the halo cells the sweep reloaded
+            xm_put<NW>(xm, (e + 1) * T & 1, w, lane, (unsigned)((e + 1) * T) + 1u, A[0] * L1[0], A[1] * L1[1]);
             ADJ_ISSUE
             PT_PROF(tsw)
         }
@@ -2309,7 +2276,6 @@ __global__ __launch_bounds__(64 * NW) void k_adj_pr(AdjPtArgs a)
             }
         }
     }
-#undef ADJR_STEP_SEL
 #undef QW
 #undef DLOAD
 #undef ADJ_ISSUE
@@ -2343,7 +2309,8 @@ __global__ __launch_bounds__(64 * NW) void k_adj_pr(AdjPtArgs a)
     }
     if (tid == 0) a.gk_part[(size_t)bs * a.nblk + tile] = red[0];
 }
-#undef ADJR_STEP
+#undef ADJR_STEP_NB
+#undef ADJR_PAIRS_NB
 #undef FWD_STEP_NB
 #undef FWD_PAIRS_NB
 #undef MIR_VERT
@@ -2698,11 +2665,8 @@ struct rdq_fwi_plan {
     int persist = 1;            // 0 off, 1 auto, 8 / 12: persistent kernels with that region height (waves),
                                 // -1: persistent launches oversubscribed 2x past residency (fault-path test)
     int xcd_mode = 1;           // persistent kernels: XCD-local slices with L2 hand-offs (pt_assign)
-    // resident workgroups (0 = unknown) per kernel variant [variant][T]: 0 fwd 64-row, 1..3 fwd 96-row
-    // with 8 / 12 / 24 rows per wave, 4 exact adjoint 64-row, 5 exact 96-row, 6 FMA adjoint 64-row,
-    // 7..8 FMA adjoint 96-row with 8 / 12 rows per wave
-    int capw[13][TB_MAXT + 1] = {};   // [9] fwd 96-row x 6 rows per wave, [10] FMA adjoint 96-row x 6,
-                                      // [11] / [12] fwd / FMA adjoint 64-row x 4 rows per wave (class 16)
+    std::vector<std::pair<const void *, int>> resident;   // resident workgroups per persistent kernel
+                                                          // queried so far (resident_capacity)
     int fwd_rw = 6, adj_rw = 6;   // rows per wave of the 96-row persistent kernels (rdq_fwi_set_rows_per_wave;
                                   // adjoint 6: 1.649 vs 1.672 ms for 8, profiles/r3/adj_rows_nb_ab.txt)
     int fwd_T = 4, adj_T = 4;   // time steps per launch (temporal blocking depth), <= TB_MAXT
@@ -2923,36 +2887,41 @@ CoefGen coef_gen(const rdq_fwi_plan *p, int B, const float *coeffs)
     return c;
 }
 
-template <int TT, bool G>
-void launch_fwd1(dim3 grid, hipStream_t st, const FwdTBArgs &a)
-{
-    hipLaunchKernelGGL(HIP_KERNEL_NAME(k_fwd_tb<TT, G>), grid, dim3(64 * TB_NW), 0, st, a);
-}
-
-void launch_fwd(int T, bool gen, dim3 grid, hipStream_t st, const FwdTBArgs &a)
-{
-    switch (T * 2 + (gen ? 1 : 0)) {
-    case 2: launch_fwd1<1, false>(grid, st, a); break;
-    case 3: launch_fwd1<1, true>(grid, st, a); break;
-    case 4: launch_fwd1<2, false>(grid, st, a); break;
-    case 5: launch_fwd1<2, true>(grid, st, a); break;
-    case 6: launch_fwd1<3, false>(grid, st, a); break;
-    case 7: launch_fwd1<3, true>(grid, st, a); break;
-    case 8: launch_fwd1<4, false>(grid, st, a); break;
-    default: launch_fwd1<4, true>(grid, st, a); break;
-    }
-}
+// ---- Kernel tables.  One function per kernel family maps the plan's settings to an instantiation:
+// the kernel and its workgroup size.  Every launch and every occupancy query goes through them, so the
+// two cannot disagree about which kernel a setting means.
+template <class Args>
+struct KernelRef {
+    void (*fn)(Args);
+    int threads;
+};
 
 template <class Args>
-void launch_adj(int T, dim3 grid, hipStream_t st, const Args &a)
+void launch_kernel(KernelRef<Args> k, unsigned grid, hipStream_t st, const Args &a)
 {
-    const dim3 blk(64 * TB_NW);
-    switch (T) {
-    case 1: hipLaunchKernelGGL(k_adj_tb<1>, grid, blk, 0, st, a); break;
-    case 2: hipLaunchKernelGGL(k_adj_tb<2>, grid, blk, 0, st, a); break;
-    case 3: hipLaunchKernelGGL(k_adj_tb<3>, grid, blk, 0, st, a); break;
-    default: hipLaunchKernelGGL(k_adj_tb<4>, grid, blk, 0, st, a); break;
-    }
+    void *argv[] = {const_cast<Args *>(&a)};
+    (void)hipLaunchKernel(reinterpret_cast<const void *>(k.fn), dim3(grid), dim3(k.threads), argv, 0, st);
+}   // (a failed launch is reported by the caller's hipGetLastError)
+
+// f(std::integral_constant<int, T>) for the run-time depth T in 1 .. N (the setters admit no other):
+// the compile-time depth of a kernel instantiation
+template <int N, class F>
+auto with_depth(int T, F &&f)
+{
+    if constexpr (N == 1) return f(std::integral_constant<int, 1>{});
+    else return T >= N ? f(std::integral_constant<int, N>{}) : with_depth<N - 1>(T, f);
+}
+
+// narrow chunked kernels (64 x 64 regions), instantiated at the plan's depth T
+KernelRef<FwdTBArgs> fwd_tb_kernel(int T, bool gen)
+{
+    return with_depth<TB_MAXT>(T, [&](auto t) -> KernelRef<FwdTBArgs> {
+        return {gen ? k_fwd_tb<t(), true> : k_fwd_tb<t(), false>, 64 * TB_NW};
+    });
+}
+KernelRef<AdjTBArgs> adj_tb_kernel(int T)
+{
+    return with_depth<TB_MAXT>(T, [](auto t) -> KernelRef<AdjTBArgs> { return {k_adj_tb<t()>, 64 * TB_NW}; });
 }
 
 // wide chunked regions: forward 16 waves x 8 rows (128 x 128), adjoint 16 waves x 4 rows (128 x 64:
@@ -2966,104 +2935,115 @@ int tw_tiles_y(int Hp, int T, bool adj)
     return (Hp + ih - 1) / ih;
 }
 
-template <int TT>
-void launch_fwd_w_T(bool gen, bool pair, dim3 grid, hipStream_t st, const FwdTBArgs &a)
-{
-    const dim3 blk(64 * TW_FWD_NW);
-    if (gen) {
-        if (pair) hipLaunchKernelGGL(HIP_KERNEL_NAME(k_fwd_tw<TT, TW_FWD_NW, TW_FWD_R, true, true>), grid, blk, 0, st, a);
-        else hipLaunchKernelGGL(HIP_KERNEL_NAME(k_fwd_tw<TT, TW_FWD_NW, TW_FWD_R, true, false>), grid, blk, 0, st, a);
-    } else {
-        if (pair) hipLaunchKernelGGL(HIP_KERNEL_NAME(k_fwd_tw<TT, TW_FWD_NW, TW_FWD_R, false, true>), grid, blk, 0, st, a);
-        else hipLaunchKernelGGL(HIP_KERNEL_NAME(k_fwd_tw<TT, TW_FWD_NW, TW_FWD_R, false, false>), grid, blk, 0, st, a);
-    }
-}
-void launch_fwd_w(int T, bool gen, bool pair, dim3 grid, hipStream_t st, const FwdTBArgs &a)
-{
-    switch (T) {
-    case 1: launch_fwd_w_T<1>(gen, pair, grid, st, a); break;
-    case 2: launch_fwd_w_T<2>(gen, pair, grid, st, a); break;
-    case 3: launch_fwd_w_T<3>(gen, pair, grid, st, a); break;
-    case 4: launch_fwd_w_T<4>(gen, pair, grid, st, a); break;
-    case 5: launch_fwd_w_T<5>(gen, pair, grid, st, a); break;
-    default: launch_fwd_w_T<6>(gen, pair, grid, st, a); break;
-    }
-}
 static_assert(FWD_W_MAX >= TW_FWD_MAXT && FWD_W_MAX >= TB_MAXT, "FwdTBArgs::w holds one sample per step of a launch");
-template <int TT, bool EX>
-void launch_adj_w_T(bool pair, dim3 grid, hipStream_t st, const AdjTBArgs &a)
+
+// wide chunked kernels, instantiated at the launch's own step count (a short tail runs as its own depth);
+// `pair`: an even padded width (two-column loads)
+KernelRef<FwdTBArgs> fwd_tw_kernel(int T, bool gen, bool pair)
 {
-    const dim3 blk(64 * TW_ADJ_NW);
-    if (pair) hipLaunchKernelGGL(HIP_KERNEL_NAME(k_adj_tw<TT, TW_ADJ_NW, TW_ADJ_R, true, EX>), grid, blk, 0, st, a);
-    else hipLaunchKernelGGL(HIP_KERNEL_NAME(k_adj_tw<TT, TW_ADJ_NW, TW_ADJ_R, false, EX>), grid, blk, 0, st, a);
+    constexpr int N = TW_FWD_NW, R = TW_FWD_R;
+    return with_depth<TW_FWD_MAXT>(T, [&](auto t) -> KernelRef<FwdTBArgs> {
+        if (gen) return {pair ? k_fwd_tw<t(), N, R, true, true> : k_fwd_tw<t(), N, R, true, false>, 64 * N};
+        return {pair ? k_fwd_tw<t(), N, R, false, true> : k_fwd_tw<t(), N, R, false, false>, 64 * N};
+    });
 }
-void launch_adj_w(int T, bool pair, bool exact, dim3 grid, hipStream_t st, const AdjTBArgs &a)
+KernelRef<AdjTBArgs> adj_tw_kernel(int T, bool pair, bool exact)
 {
-    switch (T * 2 + (exact ? 1 : 0)) {
-    case 2: launch_adj_w_T<1, false>(pair, grid, st, a); break;
-    case 3: launch_adj_w_T<1, true>(pair, grid, st, a); break;
-    case 4: launch_adj_w_T<2, false>(pair, grid, st, a); break;
-    case 5: launch_adj_w_T<2, true>(pair, grid, st, a); break;
-    case 6: launch_adj_w_T<3, false>(pair, grid, st, a); break;
-    case 7: launch_adj_w_T<3, true>(pair, grid, st, a); break;
-    case 8: launch_adj_w_T<4, false>(pair, grid, st, a); break;
-    case 9: launch_adj_w_T<4, true>(pair, grid, st, a); break;
-    case 10: launch_adj_w_T<5, false>(pair, grid, st, a); break;
-    case 11: launch_adj_w_T<5, true>(pair, grid, st, a); break;
-    case 12: launch_adj_w_T<6, false>(pair, grid, st, a); break;
-    default: launch_adj_w_T<6, true>(pair, grid, st, a); break;
-    }
+    constexpr int N = TW_ADJ_NW, R = TW_ADJ_R;
+    return with_depth<TW_ADJ_MAXT>(T, [&](auto t) -> KernelRef<AdjTBArgs> {
+        if (exact) return {pair ? k_adj_tw<t(), N, R, true, true> : k_adj_tw<t(), N, R, false, true>, 64 * N};
+        return {pair ? k_adj_tw<t(), N, R, true, false> : k_adj_tw<t(), N, R, false, false>, 64 * N};
+    });
 }
 
-// Workgroups of a persistent kernel the device holds at once (occupancy query x CUs).
-template <class K>
-int resident_capacity(K kernel, int nthreads, int &cache)
+// Depth T of the chunked kernels a plan runs, and the kernel of one chunked launch of `nsteps` steps: the
+// narrow kernels are instantiated at T whatever the launch's step count, the wide ones at `nsteps`.  (The
+// wide adjoint runs the exact order unless RDQ_VARIANT_CHUNKED_ADJ_FMA asked for the contracted stencils,
+// and only where nbc >= 20: a thin sponge's standing modes amplify the contraction.)
+int chunk_depth(const rdq_fwi_plan *p, bool adj)
 {
-    if (cache) return cache;
+    if (p->wide) return adj ? wide_adj_depth(p) : wide_fwd_depth(p);
+    return adj ? p->adj_T : p->fwd_T;
+}
+KernelRef<FwdTBArgs> chunk_fwd_kernel(const rdq_fwi_plan *p, int nsteps)
+{
+    return p->wide ? fwd_tw_kernel(nsteps, p->fwd_gen, (p->Wp & 1) == 0) : fwd_tb_kernel(p->fwd_T, p->fwd_gen);
+}
+KernelRef<AdjTBArgs> chunk_adj_kernel(const rdq_fwi_plan *p, int nsteps)
+{
+    return p->wide ? adj_tw_kernel(nsteps, (p->Wp & 1) == 0, !p->adj_tw_fma) : adj_tb_kernel(p->adj_T);
+}
+
+// Persistent kernels.  `NW` is the region class: 12 = 64 x 96 regions at the plan's rows per wave (6, 8,
+// 12 or 24 rows: 16, 12, 8 or 4 waves per workgroup), 8 = 64 x 64 regions of 8 waves x 8 rows, 16 = 64 x 64
+// regions of 16 waves x 4 rows.  The phase-profiled build exists only at T = 4.
+template <int T, bool PROF>
+KernelRef<FwdPtArgs> fwd_pt_T(int NW, int rw)
+{
+    if (NW == 16) return {k_fwd_pt<T, 16, 4, PROF>, 64 * 16};
+    if (NW != 12) return {k_fwd_pt<T, 8, 8, PROF>, 64 * 8};
+    switch (rw) {
+    case 24: return {k_fwd_pt<T, 4, 24, PROF>, 64 * 4};
+    case 12: return {k_fwd_pt<T, 8, 12, PROF>, 64 * 8};
+    case 6: return {k_fwd_pt<T, 16, 6, PROF>, 64 * 16};
+    default: return {k_fwd_pt<T, 12, 8, PROF>, 64 * 12};
+    }
+}
+KernelRef<FwdPtArgs> fwd_pt_kernel(const rdq_fwi_plan *p, int NW, int T, bool prof)
+{
+    if (prof && T == 4) return fwd_pt_T<4, true>(NW, p->fwd_rw);
+    return with_depth<TB_MAXT>(T, [&](auto t) { return fwd_pt_T<t(), false>(NW, p->fwd_rw); });
+}
+// The persistent adjoint: the FMA / recurrence build (k_adj_pr, the plan's rows per wave for 96-row
+// regions) or the oracle's exact operation order (k_adj_pt, 8 rows per wave: the 16-wave class of 64-row
+// regions pairs with its 8-wave kernel).
+template <int T, bool PROF>
+KernelRef<AdjPtArgs> adj_pt_T(int NW, int rw, bool fma)
+{
+    if (!fma) {
+        if (NW != 12) return {k_adj_pt<T, 8, PROF>, 64 * 8};
+        return {k_adj_pt<T, 12, PROF>, 64 * 12};
+    }
+    if (NW == 16) return {k_adj_pr<T, 16, 4, PROF>, 64 * 16};
+    if (NW != 12) return {k_adj_pr<T, 8, 8, PROF>, 64 * 8};
+    switch (rw) {
+    case 12: return {k_adj_pr<T, 8, 12, PROF>, 64 * 8};
+    case 6: return {k_adj_pr<T, 16, 6, PROF>, 64 * 16};
+    default: return {k_adj_pr<T, 12, 8, PROF>, 64 * 12};
+    }
+}
+KernelRef<AdjPtArgs> adj_pt_kernel(const rdq_fwi_plan *p, int NW, int T, bool fma, bool prof)
+{
+    if (prof && T == 4) return adj_pt_T<4, true>(NW, p->adj_rw, fma);
+    return with_depth<TB_MAXT>(T, [&](auto t) { return adj_pt_T<t(), false>(NW, p->adj_rw, fma); });
+}
+
+// Workgroups of a persistent kernel the device holds at once (occupancy query x CUs), remembered per
+// kernel in the plan.
+template <class Args>
+int resident_capacity(rdq_fwi_plan *p, KernelRef<Args> k)
+{
+    const void *fn = reinterpret_cast<const void *>(k.fn);
+    for (const auto &e : p->resident)
+        if (e.first == fn) return e.second;
     int dev = 0, cus = 0, nb = 0;
     if (hipGetDevice(&dev) != hipSuccess) return -1;
     if (hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess) return -1;
-    if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&nb, kernel, nthreads, 0) != hipSuccess) return -1;
-    cache = cus * nb;
-    return cache;
+    if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&nb, fn, k.threads, 0) != hipSuccess) return -1;
+    if (cus * nb) p->resident.emplace_back(fn, cus * nb);
+    return cus * nb;
 }
 
-// Resident capacity of the persistent kernel a call would launch (occupancy query x CUs).  `NW` is
-// the region-height class (region rows = NW x 8: 64 or 96); the 96-row kernels run 8, 12 or 24 rows
-// per wave (12, 8 or 4 waves per workgroup).  The adjoint's launch must fit both adjoint variants.
-template <int T>
-int capacity_T(rdq_fwi_plan *p, int NW, bool adj)
-{
-    auto *c = p->capw;
-    if (!adj) {
-        if (NW == 16) return resident_capacity(k_fwd_pt<T, 16, 4, false>, 1024, c[11][T]);
-        if (NW != 12) return resident_capacity(k_fwd_pt<T, 8, 8, false>, 512, c[0][T]);
-        if (p->fwd_rw == 24) return resident_capacity(k_fwd_pt<T, 4, 24, false>, 256, c[3][T]);
-        if (p->fwd_rw == 6) return resident_capacity(k_fwd_pt<T, 16, 6, false>, 1024, c[9][T]);
-        if (p->fwd_rw == 12) return resident_capacity(k_fwd_pt<T, 8, 12, false>, 512, c[2][T]);
-        return resident_capacity(k_fwd_pt<T, 12, 8, false>, 768, c[1][T]);
-    }
-    if (NW != 12)
-        return std::min(resident_capacity(k_adj_pt<T, 8, false>, 512, c[4][T]),
-                        NW == 16 ? resident_capacity(k_adj_pr<T, 16, 4, false>, 1024, c[12][T])
-                                 : resident_capacity(k_adj_pr<T, 8, 8, false>, 512, c[6][T]));
-    const int ex = resident_capacity(k_adj_pt<T, 12, false>, 768, c[5][T]);
-    if (p->adj_rw == 12) return std::min(ex, resident_capacity(k_adj_pr<T, 8, 12, false>, 512, c[8][T]));
-    if (p->adj_rw == 6) return std::min(ex, resident_capacity(k_adj_pr<T, 16, 6, false>, 1024, c[10][T]));
-    return std::min(ex, resident_capacity(k_adj_pr<T, 12, 8, false>, 768, c[7][T]));
-}
+// Resident capacity of the persistent kernel a call would launch.  The adjoint's launch must fit both
+// adjoint variants of the class, whichever one adj_fma selects.
 int capacity_nw(rdq_fwi_plan *p, int NW, bool adj, int T)
 {
-    switch (T) {
-    case 1: return capacity_T<1>(p, NW, adj);
-    case 2: return capacity_T<2>(p, NW, adj);
-    case 3: return capacity_T<3>(p, NW, adj);
-    default: return capacity_T<4>(p, NW, adj);
-    }
+    if (!adj) return resident_capacity(p, fwd_pt_kernel(p, NW, T, false));
+    return std::min(resident_capacity(p, adj_pt_kernel(p, NW, T, false, false)),
+                    resident_capacity(p, adj_pt_kernel(p, NW, T, true, false)));
 }
 
-// Region classes of the persistent kernels: 12 = 64 x 96 regions (the plan's rows per wave),
-// 8 = 64 x 64 regions of 8 waves x 8 rows, 16 = 64 x 64 regions of 16 waves x 4 rows.
+// rows of a persistent region of class NW (fwd_pt_T)
 static int region_rows(int NW) { return NW == 12 ? 96 : 64; }
 
 // tiles (padded to the 8-XCD deal) of one (model, shot) slice at depth T with NW-wave regions
@@ -3159,53 +3139,6 @@ int persistent_nw(rdq_fwi_plan *p, int B, bool adj, int *per = nullptr)
     return 0;
 }
 
-// the persistent forward of region class NW (64 / 96 rows) with the plan's rows per wave
-template <int T, bool PROF>
-void launch_fwd_pt_T(const rdq_fwi_plan *p, int NW, dim3 grid, hipStream_t st, const FwdPtArgs &a)
-{
-    if (NW == 16) hipLaunchKernelGGL(HIP_KERNEL_NAME(k_fwd_pt<T, 16, 4, PROF>), grid, dim3(1024), 0, st, a);
-    else if (NW != 12) hipLaunchKernelGGL(HIP_KERNEL_NAME(k_fwd_pt<T, 8, 8, PROF>), grid, dim3(512), 0, st, a);
-    else if (p->fwd_rw == 24) hipLaunchKernelGGL(HIP_KERNEL_NAME(k_fwd_pt<T, 4, 24, PROF>), grid, dim3(256), 0, st, a);
-    else if (p->fwd_rw == 12) hipLaunchKernelGGL(HIP_KERNEL_NAME(k_fwd_pt<T, 8, 12, PROF>), grid, dim3(512), 0, st, a);
-    else if (p->fwd_rw == 6) hipLaunchKernelGGL(HIP_KERNEL_NAME(k_fwd_pt<T, 16, 6, PROF>), grid, dim3(1024), 0, st, a);
-    else hipLaunchKernelGGL(HIP_KERNEL_NAME(k_fwd_pt<T, 12, 8, PROF>), grid, dim3(768), 0, st, a);
-}
-void launch_fwd_pt(const rdq_fwi_plan *p, int NW, int T, dim3 grid, hipStream_t st, const FwdPtArgs &a)
-{
-    if (a.prof && T == 4) { launch_fwd_pt_T<4, true>(p, NW, grid, st, a); return; }   // phase-profiled build
-    switch (T) {
-    case 1: launch_fwd_pt_T<1, false>(p, NW, grid, st, a); break;
-    case 2: launch_fwd_pt_T<2, false>(p, NW, grid, st, a); break;
-    case 3: launch_fwd_pt_T<3, false>(p, NW, grid, st, a); break;
-    default: launch_fwd_pt_T<4, false>(p, NW, grid, st, a); break;
-    }
-}
-
-// the persistent adjoint: FMA / recurrence build (k_adj_pr, the plan's rows per wave for 96-row
-// regions) or the oracle's exact operation order (k_adj_pt, 8 rows per wave)
-template <int T, bool PROF>
-void launch_adj_pt_T(const rdq_fwi_plan *p, int NW, dim3 grid, hipStream_t st, const AdjPtArgs &a)
-{
-    if (!p->adj_fma) {
-        if (NW != 12) hipLaunchKernelGGL(HIP_KERNEL_NAME(k_adj_pt<T, 8, PROF>), grid, dim3(512), 0, st, a);
-        else hipLaunchKernelGGL(HIP_KERNEL_NAME(k_adj_pt<T, 12, PROF>), grid, dim3(768), 0, st, a);
-    } else if (NW == 16) hipLaunchKernelGGL(HIP_KERNEL_NAME(k_adj_pr<T, 16, 4, PROF>), grid, dim3(1024), 0, st, a);
-    else if (NW != 12) hipLaunchKernelGGL(HIP_KERNEL_NAME(k_adj_pr<T, 8, 8, PROF>), grid, dim3(512), 0, st, a);
-    else if (p->adj_rw == 12) hipLaunchKernelGGL(HIP_KERNEL_NAME(k_adj_pr<T, 8, 12, PROF>), grid, dim3(512), 0, st, a);
-    else if (p->adj_rw == 6) hipLaunchKernelGGL(HIP_KERNEL_NAME(k_adj_pr<T, 16, 6, PROF>), grid, dim3(1024), 0, st, a);
-    else hipLaunchKernelGGL(HIP_KERNEL_NAME(k_adj_pr<T, 12, 8, PROF>), grid, dim3(768), 0, st, a);
-}
-void launch_adj_pt(const rdq_fwi_plan *p, int NW, int T, dim3 grid, hipStream_t st, const AdjPtArgs &a)
-{
-    if (a.prof && T == 4) { launch_adj_pt_T<4, true>(p, NW, grid, st, a); return; }   // phase-profiled build
-    switch (T) {
-    case 1: launch_adj_pt_T<1, false>(p, NW, grid, st, a); break;
-    case 2: launch_adj_pt_T<2, false>(p, NW, grid, st, a); break;
-    case 3: launch_adj_pt_T<3, false>(p, NW, grid, st, a); break;
-    default: launch_adj_pt_T<4, false>(p, NW, grid, st, a); break;
-    }
-}
-
 // The buffers a launch needs zeroed (granules, accumulators, history slots, adjoint levels, pt_assign's
 // arrival counters) in ONE stream-ordered kernel instead of a memset each (each memset is a separate
 // ~5 us dispatch on the step's critical path).  Sizes are multiples of 4 B; 16-byte-aligned regions are
@@ -3286,9 +3219,9 @@ int launch_forward_pt(rdq_fwi_plan *p, int B, int NW, int per, const float *coef
     for (int s0 = 0; s0 < B * p->g.ns; s0 += per) {
         a.g.sl_off = s0;
         a.g.nsl = std::min(per, B * p->g.ns - s0);
-        const dim3 grid(pt_grid(p, T, NW, a.g.nsl, false));
+        const unsigned grid = pt_grid(p, T, NW, a.g.nsl, false);
         if (s0 > 0) RDQ_TRY(zero_regions({{p->d_status + 16, 8 * sizeof(unsigned)}}, st));   // pt_assign arrivals
-        launch_fwd_pt(p, NW, T, grid, st, a);
+        launch_kernel(fwd_pt_kernel(p, NW, T, a.prof != nullptr), grid, st, a);
         RDQ_CHECK(hipGetLastError());
     }
     return 0;
@@ -3319,123 +3252,13 @@ int launch_adjoint_pt(rdq_fwi_plan *p, int B, int NW, int per, const float *coef
     for (int s0 = 0; s0 < B * p->g.ns; s0 += per) {
         a.g.sl_off = s0;
         a.g.nsl = std::min(per, B * p->g.ns - s0);
-        const dim3 grid(pt_grid(p, T, NW, a.g.nsl, true));
+        const unsigned grid = pt_grid(p, T, NW, a.g.nsl, true);
         if (s0 > 0) RDQ_TRY(zero_regions({{p->d_status + 16, 8 * sizeof(unsigned)}}, st));   // pt_assign arrivals
-        launch_adj_pt(p, NW, T, grid, st, a);
+        launch_kernel(adj_pt_kernel(p, NW, T, p->adj_fma, a.prof != nullptr), grid, st, a);
         RDQ_CHECK(hipGetLastError());
     }
     return 0;
 }
-
-int launch_forward(rdq_fwi_plan *p, int B, const float *coeffs, float *seis, float *hist,
-                   float *ring, hipStream_t st)
-{
-    FwdTBArgs a{};
-    a.g = tb_geo(p, B);
-    const size_t L = a.g.level;
-    const int T = p->wide ? wide_fwd_depth(p) : p->fwd_T, S = chain_count(p), ns = p->g.ns;
-    // (no hipMemsetAsync under graph capture: see zero_regions)
-    if (hist) RDQ_TRY(zero_regions({{hist, 2 * L * sizeof(float)}}, st));
-    else RDQ_TRY(zero_regions({{ring, 4 * L * sizeof(float)}}, st));
-    a.coeffs = coeffs;
-    a.cg = coef_gen(p, B, coeffs);
-    a.seis = seis;
-    a.hist = hist;
-    RDQ_TRY(fork_chains(p, st, S));
-    const int nt = p->g.nt;
-    for (int c = 0; c < S; ++c) {
-        a.g.s_off = c * ns / S;
-        a.g.ns_grp = (c + 1) * ns / S - a.g.s_off;
-        a.ns_sh = a.g.ns_grp;            // wide kernels: a.spw shots of one region per workgroup
-        const hipStream_t cs = c == 0 ? st : p->aux[c - 1];
-        for (int n0 = 0, i = 0; n0 < nt; n0 += T, ++i) {
-            a.n0 = n0;
-            a.nsteps = std::min(T, nt - n0);
-            // tile grid of this launch's depth (the wide kernels run a short tail as its own T)
-            const int Tl = p->wide ? a.nsteps : T;
-            a.g.tiles_x = p->wide ? tw_tiles_x(p->Wp, Tl) : tiles_x(p->Wp, Tl);
-            a.g.ntiles = a.g.tiles_x * (p->wide ? tw_tiles_y(p->Hp, Tl, false) : tiles_y(p->Hp, Tl));
-            a.spw = p->wide ? wide_spw(p->fwd_spw, B * a.g.ntiles, a.ns_sh, false, S) : 1;
-            a.g.ns_grp = (a.ns_sh + a.spw - 1) / a.spw;
-            const dim3 grid((a.g.ntiles + 7) / 8 * 8 * B * a.g.ns_grp);
-            for (int t = 0; t < FWD_W_MAX; ++t) a.w[t] = t < a.nsteps ? p->wavf[n0 + t] : 0.0f;
-            if (hist) {
-                a.in_prev = hist + (size_t)n0 * L;          // slot n0   = P_{n0-1}
-                a.in_cur = hist + (size_t)(n0 + 1) * L;     // slot n0+1 = P_{n0}
-                a.out_prev = a.out_cur = nullptr;
-            } else {
-                const int pin = i & 1, pout = pin ^ 1;
-                a.in_prev = ring + (size_t)(2 * pin) * L;
-                a.in_cur = ring + (size_t)(2 * pin + 1) * L;
-                a.out_prev = ring + (size_t)(2 * pout) * L;
-                a.out_cur = ring + (size_t)(2 * pout + 1) * L;
-            }
-            if (p->wide) launch_fwd_w(a.nsteps, p->fwd_gen, (p->Wp & 1) == 0, grid, cs, a);   // (tail: T' < T)
-            else launch_fwd(T, p->fwd_gen, grid, cs, a);
-        }
-    }
-    RDQ_CHECK(hipGetLastError());
-    return join_chains(p, st, S);
-}
-
-int launch_adjoint(rdq_fwi_plan *p, int B, const float *coeffs, const float *hist,
-                   const float *dseis, float *ring, float *gA, double *gk, float *gbeta, hipStream_t st)
-{
-    AdjTBArgs a{};
-    a.g = tb_geo(p, B);
-    const size_t L = a.g.level;
-    const int T = p->wide ? wide_adj_depth(p) : p->adj_T, S = chain_count(p), ns = p->g.ns;
-    const int nblk_alloc = gk_blocks(p);
-    a.coeffs = coeffs; a.hist = hist; a.dseis = dseis; a.gA = gA; a.gk_part = gk; a.gbeta = gbeta;
-    a.cg = coef_gen(p, B, coeffs);
-    a.nblk = nblk_alloc;
-    // launch geometry of chain c's launch of depth nsteps: sets a.g.{s_off, tiles_x, ntiles, ns_grp},
-    // a.ns_sh, a.spw; returns the grid size
-    auto geometry = [&](int c, int nsteps) -> unsigned {
-        a.g.s_off = c * ns / S;
-        a.ns_sh = (c + 1) * ns / S - a.g.s_off;   // wide kernels: a.spw shots of one region per workgroup
-        const int Tl = p->wide ? nsteps : T;
-        a.g.tiles_x = p->wide ? tw_tiles_x(p->Wp, Tl) : tiles_x(p->Wp, Tl);
-        a.g.ntiles = a.g.tiles_x * (p->wide ? tw_tiles_y(p->Hp, Tl, true) : tiles_y(p->Hp, Tl));
-        a.spw = p->wide ? wide_spw(p->adj_spw, B * a.g.ntiles, a.ns_sh, true, S) : 1;
-        a.g.ns_grp = (a.ns_sh + a.spw - 1) / a.spw;   // (the decode's slice groups are shot groups)
-        return (unsigned)((a.g.ntiles + 7) / 8 * 8 * B * a.g.ns_grp);
-    };
-    {   // the gk_part one-writer invariant, on every launch, before anything is enqueued
-        GkWriters writers((size_t)B * ns, nblk_alloc);
-        for (int c = 0; c < S; ++c)
-            for (int k0 = p->g.nt; k0 >= 1; k0 -= T) {
-                const unsigned grid = geometry(c, std::min(T, k0));
-                if (!writers.add(c, grid, a.g.tiles_x, a.g.ntiles, B, ns, a.g.ns_grp, a.g.s_off, a.spw, a.ns_sh))
-                    return RDQ_E_INVALID;
-            }
-    }
-    RDQ_TRY(zero_regions({{ring, 4 * L * sizeof(float)}, {gA, L * sizeof(float)},
-                          {gk, (size_t)B * ns * nblk_alloc * sizeof(double)}, {gbeta, (size_t)B * ns * sizeof(float)}},
-                         st));   // (no hipMemsetAsync under graph capture: see zero_regions)
-    RDQ_TRY(fork_chains(p, st, S));
-    for (int c = 0; c < S; ++c) {
-        const hipStream_t cs = c == 0 ? st : p->aux[c - 1];
-        for (int k0 = p->g.nt, i = 0; k0 >= 1; k0 -= T, ++i) {
-            a.k0 = k0;
-            a.nsteps = std::min(T, k0);
-            const dim3 grid(geometry(c, a.nsteps));
-            for (int t = 0; t < ADJ_W_MAX; ++t) a.w[t] = t < a.nsteps ? p->wavf[k0 - 1 - t] : 0.0f;
-            const int pin = i & 1, pout = pin ^ 1;
-            a.in_l1 = ring + (size_t)(2 * pin) * L;
-            a.in_l2 = ring + (size_t)(2 * pin + 1) * L;
-            a.out_l1 = ring + (size_t)(2 * pout) * L;
-            a.out_l2 = ring + (size_t)(2 * pout + 1) * L;
-            // (tail: T' < T); the exact order unless RDQ_VARIANT_CHUNKED_ADJ_FMA asked for the contracted
-            // stencils (and only where nbc >= 20: a thin sponge's standing modes amplify the contraction)
-            if (p->wide) launch_adj_w(a.nsteps, (p->Wp & 1) == 0, !p->adj_tw_fma, grid, cs, a);
-            else launch_adj(T, grid, cs, a);
-        }
-    }
-    RDQ_CHECK(hipGetLastError());
-    return join_chains(p, st, S);
-}
-
 
 // ---- Checkpointed gradient (rdq_fwi_forward_ckpt / rdq_fwi_adjoint_ckpt): the history bounded by
 // recomputation.  Segments of K steps are counted from the END of the record: boundaries b_c =
@@ -3473,157 +3296,171 @@ __global__ __launch_bounds__(256) void k_ckpt_levels(const float *src, float *ds
         dst[base + i] = src ? src[base + i] : 0.0f;
 }
 
-// First pass of a checkpointed gradient: the no-grad chunked forward (ring ping-pong) with its launches
-// cut at the segment boundaries; the launch that ends on an interior boundary writes its two output
-// levels into the checkpoint store instead of the ring, and the next launch reads them from there (no
-// copy).  Seismograms as rdq_fwi_forward's.
-int launch_forward_ckpt(rdq_fwi_plan *p, int B, int K, const float *coeffs, float *seis, float *ckpt, float *ring,
-                        hipStream_t st)
+// ---- The chunked time loops as data.  A chunked call is a schedule: per launch chain, the ordered list of
+// its launches, built by chunked_schedule from the segments of a CkptPlan (store-all = the one-segment plan)
+// and the plan's settings.  enqueue_chunked checks and launches it; rdq_fwi_launch_info, rdq_fwi_wide_info
+// and rdq_fwi_ckpt_info count it.  The four passes:
+//   fwd_ring  the no-grad forward (ring ping-pong, seismograms), its launches cut at the segment
+//             boundaries: the launch that ends on an interior boundary writes its two output levels into
+//             the checkpoint store instead of the ring, and the next launch reads them from there (no copy);
+//   fwd_hist  the history form over one segment: level j of the buffer = slot hbase + j, levels 0 and 1
+//             given (zeroed for the whole record, hbase = 0), every launch writes its steps' levels;
+//   adj_hist  the adjoint over a stored history (one segment, hbase = 0);
+//   adj_ckpt  per segment, from the last to the first: the segment buffer's levels 0 and 1 from the
+//             checkpoint (k_ckpt_levels), the fwd_hist launches of the segment (hbase = lo: the recompute,
+//             no seismograms), then its adjoint launches (dseis, wavelet and record indices stay absolute).
+// The adjoint's levels stay in the ring between launches and the ring parity runs on across segments.
+// Every launch of a chain is ordered on the chain's stream, so a segment's recompute overwrites the
+// segment buffer only after the previous segment's adjoint has read it.
+enum class Pass { fwd_ring, fwd_hist, adj_hist, adj_ckpt };
+enum class Store { none, ring, ckpt, hist };
+struct LevelPair {                   // two consecutive levels {slot, slot + 1} of a store (none: nullptr)
+    Store store;
+    int slot;
+};
+struct Launch {
+    enum Kind { levels, fwd, adj } kind;
+    int chain, s_off, ns_sh;         // launch chain and its shots [s_off, s_off + ns_sh) of every model
+    int first, nsteps;               // fwd: steps first, first + 1, ...; adj: steps first, first - 1, ...
+    int seg, hbase;                  // segment, and the slot held by the history buffer's first level
+    int tiles_x, ntiles, spw, ns_grp;   // tile grid of the launch's depth, shots per workgroup, shot groups
+    unsigned grid;
+    LevelPair in, out;               // levels read and written (fwd into a history: out = none)
+};
+
+std::vector<Launch> chunked_schedule(const rdq_fwi_plan *p, int B, Pass pass, const CkptPlan &cp)
 {
-    const CkptPlan cp = ckpt_plan(p, K);
-    FwdTBArgs a{};
-    a.g = tb_geo(p, B);
-    const size_t L = a.g.level;
-    const int T = p->wide ? wide_fwd_depth(p) : p->fwd_T, S = chain_count(p), ns = p->g.ns;
-    RDQ_TRY(zero_regions({{ring, 4 * L * sizeof(float)}}, st));   // (no hipMemsetAsync under graph capture)
-    a.coeffs = coeffs;
-    a.cg = coef_gen(p, B, coeffs);
-    a.seis = seis;
-    a.hist = nullptr;
-    RDQ_TRY(fork_chains(p, st, S));
+    const int Tf = chunk_depth(p, false), Ta = chunk_depth(p, true), S = chain_count(p), ns = p->g.ns;
+    std::vector<Launch> sched;
+    auto add = [&](Launch::Kind kind, int c, int sg, int first, int nsteps, LevelPair in, LevelPair out) {
+        Launch l{};
+        l.kind = kind; l.chain = c; l.seg = sg; l.first = first; l.nsteps = nsteps; l.in = in; l.out = out;
+        l.hbase = pass == Pass::fwd_ring ? 0 : cp.lo(sg);
+        l.s_off = c * ns / S;
+        l.ns_sh = (c + 1) * ns / S - l.s_off;
+        if (kind != Launch::levels) {
+            // tile grid of this launch's depth (the wide kernels run a short tail as its own depth); wide
+            // kernels: spw shots of one region per workgroup (the decode's slice groups are shot groups)
+            const bool adj = kind == Launch::adj;
+            const int Tl = p->wide ? nsteps : (adj ? Ta : Tf);
+            l.tiles_x = p->wide ? tw_tiles_x(p->Wp, Tl) : tiles_x(p->Wp, Tl);
+            l.ntiles = l.tiles_x * (p->wide ? tw_tiles_y(p->Hp, Tl, adj) : tiles_y(p->Hp, Tl));
+            l.spw = p->wide ? wide_spw(adj ? p->adj_spw : p->fwd_spw, B * l.ntiles, l.ns_sh, adj, S) : 1;
+            l.ns_grp = (l.ns_sh + l.spw - 1) / l.spw;
+            l.grid = (unsigned)((l.ntiles + 7) / 8 * 8 * B * l.ns_grp);
+        }
+        sched.push_back(l);
+    };
     for (int c = 0; c < S; ++c) {
-        a.g.s_off = c * ns / S;
-        a.ns_sh = (c + 1) * ns / S - a.g.s_off;
-        const hipStream_t cs = c == 0 ? st : p->aux[c - 1];
         int i = 0;                                               // ring parity: runs on across segments
-        for (int sg = cp.nseg - 1; sg >= 0; --sg) {
-            const int lo = cp.lo(sg), hi = cp.hi(sg);
-            for (int n0 = lo; n0 < hi; n0 += T, ++i) {
-                a.n0 = n0;
-                a.nsteps = std::min(T, hi - n0);
-                const int Tl = p->wide ? a.nsteps : T;
-                a.g.tiles_x = p->wide ? tw_tiles_x(p->Wp, Tl) : tiles_x(p->Wp, Tl);
-                a.g.ntiles = a.g.tiles_x * (p->wide ? tw_tiles_y(p->Hp, Tl, false) : tiles_y(p->Hp, Tl));
-                a.spw = p->wide ? wide_spw(p->fwd_spw, B * a.g.ntiles, a.ns_sh, false, S) : 1;
-                a.g.ns_grp = (a.ns_sh + a.spw - 1) / a.spw;
-                const dim3 grid((a.g.ntiles + 7) / 8 * 8 * B * a.g.ns_grp);
-                for (int t = 0; t < FWD_W_MAX; ++t) a.w[t] = t < a.nsteps ? p->wavf[n0 + t] : 0.0f;
-                const int pin = i & 1, pout = pin ^ 1;
-                if (n0 == lo && lo > 0) {                        // checkpoint sg + 1 = pair sg
-                    a.in_prev = ckpt + (size_t)(2 * sg) * L;
-                    a.in_cur = ckpt + (size_t)(2 * sg + 1) * L;
-                } else {
-                    a.in_prev = ring + (size_t)(2 * pin) * L;
-                    a.in_cur = ring + (size_t)(2 * pin + 1) * L;
-                }
-                if (n0 + a.nsteps == hi && hi < cp.nt) {         // checkpoint sg = pair sg - 1
-                    a.out_prev = ckpt + (size_t)(2 * (sg - 1)) * L;
-                    a.out_cur = ckpt + (size_t)(2 * (sg - 1) + 1) * L;
-                } else {
-                    a.out_prev = ring + (size_t)(2 * pout) * L;
-                    a.out_cur = ring + (size_t)(2 * pout + 1) * L;
-                }
-                if (p->wide) launch_fwd_w(a.nsteps, p->fwd_gen, (p->Wp & 1) == 0, grid, cs, a);
-                else launch_fwd(T, p->fwd_gen, grid, cs, a);
+        if (pass == Pass::fwd_ring) {
+            for (int sg = cp.nseg - 1; sg >= 0; --sg) {
+                const int lo = cp.lo(sg), hi = cp.hi(sg);
+                for (int n0 = lo; n0 < hi; n0 += Tf, ++i) {
+                    const int n = std::min(Tf, hi - n0), pin = i & 1, pout = pin ^ 1;
+                    add(Launch::fwd, c, sg, n0, n,
+                        n0 == lo && lo > 0 ? LevelPair{Store::ckpt, 2 * sg} : LevelPair{Store::ring, 2 * pin},
+                        n0 + n == hi && hi < cp.nt ? LevelPair{Store::ckpt, 2 * (sg - 1)} : LevelPair{Store::ring, 2 * pout});
+                }                                                // (checkpoint sg = pair sg - 1 of the store)
             }
+            continue;
+        }
+        for (int sg = 0; sg < cp.nseg; ++sg) {
+            const int lo = cp.lo(sg), hi = cp.hi(sg);
+            if (pass == Pass::adj_ckpt)   // slots lo, lo + 1: checkpoint sg + 1 = pair sg, or zeros at the record's start
+                add(Launch::levels, c, sg, lo, 0, lo > 0 ? LevelPair{Store::ckpt, 2 * sg} : LevelPair{Store::none, 0},
+                    LevelPair{Store::hist, 0});
+            if (pass != Pass::adj_hist)   // slot n0 = P_{n0-1}, slot n0 + 1 = P_{n0}; writes slots lo + 2 .. hi + 1
+                for (int n0 = lo; n0 < hi; n0 += Tf)
+                    add(Launch::fwd, c, sg, n0, std::min(Tf, hi - n0), LevelPair{Store::hist, n0 - lo},
+                        LevelPair{Store::none, 0});
+            if (pass != Pass::fwd_hist)   // adjoint steps k = hi .. lo + 1: slots lo + 1 .. hi
+                for (int k0 = hi; k0 > lo; k0 -= Ta, ++i) {
+                    const int pin = i & 1, pout = pin ^ 1;
+                    add(Launch::adj, c, sg, k0, std::min(Ta, k0 - lo), LevelPair{Store::ring, 2 * pin},
+                        LevelPair{Store::ring, 2 * pout});
+                }
         }
     }
-    RDQ_CHECK(hipGetLastError());
-    return join_chains(p, st, S);
+    return sched;
 }
 
-// Backward of a checkpointed gradient: the segments from the last to the first; each one's levels are
-// recomputed from its checkpoint into `seg` (level j of seg = the history's slot lo + j: the chunked
-// forward's history form with FwdTBArgs::hbase = lo, recording no seismograms), then the chunked adjoint
-// runs over it (AdjTBArgs::hbase = lo; dseis, wavelet and record indices stay absolute).  The adjoint's
-// levels stay in `ring` between launches and its ring parity runs on across segments; ring, gA, gk_part
-// and gbeta are zeroed once.  Every launch of a chain is ordered on the chain's stream, so a segment's
-// recompute overwrites `seg` only after the previous segment's adjoint has read it.
-int launch_adjoint_ckpt(rdq_fwi_plan *p, int B, int K, const float *coeffs, const float *ckpt, float *seg,
-                        const float *dseis, float *ring, float *gA, double *gk, float *gbeta, hipStream_t st)
+// launches of one kind that chain 0 runs (every chain runs the same number)
+int count_launches(const std::vector<Launch> &sched, Launch::Kind kind)
 {
-    const CkptPlan cp = ckpt_plan(p, K);
+    int n = 0;
+    for (const Launch &l : sched) n += l.chain == 0 && l.kind == kind;
+    return n;
+}
+
+// The buffers of a chunked call; a pass leaves the ones it does not use null.  `hist` is the stored
+// history or the checkpointed segment buffer.
+struct ChunkBufs {
+    const float *coeffs;
+    float *seis, *hist, *ckpt, *ring;
+    const float *dseis;
+    float *gA;
+    double *gk;
+    float *gbeta;
+};
+
+int enqueue_chunked(rdq_fwi_plan *p, int B, Pass pass, int K, const ChunkBufs &b, hipStream_t st)
+{
+    const std::vector<Launch> sched = chunked_schedule(p, B, pass, ckpt_plan(p, K));
     FwdTBArgs f{};
     AdjTBArgs a{};
     f.g = a.g = tb_geo(p, B);
     const size_t L = a.g.level, slice = a.g.slice;
-    const int Tf = p->wide ? wide_fwd_depth(p) : p->fwd_T, Ta = p->wide ? wide_adj_depth(p) : p->adj_T;
-    const int S = chain_count(p), ns = p->g.ns;
-    const int nblk_alloc = gk_blocks(p);
-    f.coeffs = coeffs; f.cg = coef_gen(p, B, coeffs); f.seis = nullptr; f.hist = seg;
-    f.out_prev = f.out_cur = nullptr;
-    a.coeffs = coeffs; a.hist = seg; a.dseis = dseis; a.gA = gA; a.gk_part = gk; a.gbeta = gbeta;
-    a.cg = f.cg;
-    a.nblk = nblk_alloc;
-    auto geometry = [&](int c, int nsteps) -> unsigned {          // (launch_adjoint's)
-        a.g.s_off = c * ns / S;
-        a.ns_sh = (c + 1) * ns / S - a.g.s_off;
-        const int Tl = p->wide ? nsteps : Ta;
-        a.g.tiles_x = p->wide ? tw_tiles_x(p->Wp, Tl) : tiles_x(p->Wp, Tl);
-        a.g.ntiles = a.g.tiles_x * (p->wide ? tw_tiles_y(p->Hp, Tl, true) : tiles_y(p->Hp, Tl));
-        a.spw = p->wide ? wide_spw(p->adj_spw, B * a.g.ntiles, a.ns_sh, true, S) : 1;
-        a.g.ns_grp = (a.ns_sh + a.spw - 1) / a.spw;
-        return (unsigned)((a.g.ntiles + 7) / 8 * 8 * B * a.g.ns_grp);
-    };
-    {   // the gk_part one-writer invariant, on every adjoint launch of every segment, before anything is enqueued
+    const int S = chain_count(p), ns = p->g.ns, nblk_alloc = gk_blocks(p);
+    const bool adjoint = pass == Pass::adj_hist || pass == Pass::adj_ckpt;
+    if (adjoint) {   // the gk_part one-writer invariant, on every adjoint launch, before anything is enqueued
         GkWriters writers((size_t)B * ns, nblk_alloc);
-        for (int c = 0; c < S; ++c)
-            for (int sg = 0; sg < cp.nseg; ++sg)
-                for (int k0 = cp.hi(sg); k0 > cp.lo(sg); k0 -= Ta) {
-                    const unsigned grid = geometry(c, std::min(Ta, k0 - cp.lo(sg)));
-                    if (!writers.add(c, grid, a.g.tiles_x, a.g.ntiles, B, ns, a.g.ns_grp, a.g.s_off, a.spw, a.ns_sh))
-                        return RDQ_E_INVALID;
-                }
+        for (const Launch &l : sched)
+            if (l.kind == Launch::adj &&
+                !writers.add(l.chain, l.grid, l.tiles_x, l.ntiles, B, ns, l.ns_grp, l.s_off, l.spw, l.ns_sh))
+                return RDQ_E_INVALID;
     }
-    RDQ_TRY(zero_regions({{ring, 4 * L * sizeof(float)}, {gA, L * sizeof(float)},
-                          {gk, (size_t)B * ns * nblk_alloc * sizeof(double)}, {gbeta, (size_t)B * ns * sizeof(float)}},
-                         st));   // once, before the last segment (no hipMemsetAsync under graph capture)
+    // zeroed once, ahead of the chains (no hipMemsetAsync under graph capture: see zero_regions)
+    if (adjoint)
+        RDQ_TRY(zero_regions({{b.ring, 4 * L * sizeof(float)}, {b.gA, L * sizeof(float)},
+                              {b.gk, (size_t)B * ns * nblk_alloc * sizeof(double)},
+                              {b.gbeta, (size_t)B * ns * sizeof(float)}}, st));
+    else if (pass == Pass::fwd_hist) RDQ_TRY(zero_regions({{b.hist, 2 * L * sizeof(float)}}, st));
+    else RDQ_TRY(zero_regions({{b.ring, 4 * L * sizeof(float)}}, st));
+    f.coeffs = a.coeffs = b.coeffs;
+    f.cg = a.cg = coef_gen(p, B, b.coeffs);
+    f.seis = b.seis; f.hist = b.hist;
+    a.hist = b.hist; a.dseis = b.dseis; a.gA = b.gA; a.gk_part = b.gk; a.gbeta = b.gbeta;
+    a.nblk = nblk_alloc;
+    auto level = [&](LevelPair lp, int j) -> float * {
+        float *base = lp.store == Store::ring ? b.ring : lp.store == Store::ckpt ? b.ckpt
+                      : lp.store == Store::hist ? b.hist : nullptr;
+        return base ? base + (size_t)(lp.slot + j) * L : nullptr;
+    };
     RDQ_TRY(fork_chains(p, st, S));
-    for (int c = 0; c < S; ++c) {
-        const hipStream_t cs = c == 0 ? st : p->aux[c - 1];
-        const int s_off = c * ns / S, ns_sh = (c + 1) * ns / S - s_off;
-        int i = 0;                                               // the adjoint's ring parity
-        for (int sg = 0; sg < cp.nseg; ++sg) {
-            const int lo = cp.lo(sg), hi = cp.hi(sg);
-            {   // slots lo, lo + 1: checkpoint sg + 1 = pair sg, or zeros at the start of the record
-                const size_t run = (size_t)ns_sh * slice;
-                const unsigned gx = (unsigned)std::min<size_t>((run + 255) / 256, 1024);
-                hipLaunchKernelGGL(k_ckpt_levels, dim3(gx, 2 * B), dim3(256), 0, cs,
-                                   lo > 0 ? ckpt + (size_t)(2 * sg) * L : nullptr, seg, L, (size_t)ns * slice,
-                                   (size_t)s_off * slice, run, B);
-            }
-            f.hbase = lo;
-            f.g.s_off = s_off;
-            f.ns_sh = ns_sh;
-            for (int n0 = lo; n0 < hi; n0 += Tf) {               // recompute: slots lo + 2 .. hi + 1
-                f.n0 = n0;
-                f.nsteps = std::min(Tf, hi - n0);
-                const int Tl = p->wide ? f.nsteps : Tf;
-                f.g.tiles_x = p->wide ? tw_tiles_x(p->Wp, Tl) : tiles_x(p->Wp, Tl);
-                f.g.ntiles = f.g.tiles_x * (p->wide ? tw_tiles_y(p->Hp, Tl, false) : tiles_y(p->Hp, Tl));
-                f.spw = p->wide ? wide_spw(p->fwd_spw, B * f.g.ntiles, f.ns_sh, false, S) : 1;
-                f.g.ns_grp = (f.ns_sh + f.spw - 1) / f.spw;
-                const dim3 grid((f.g.ntiles + 7) / 8 * 8 * B * f.g.ns_grp);
-                for (int t = 0; t < FWD_W_MAX; ++t) f.w[t] = t < f.nsteps ? p->wavf[n0 + t] : 0.0f;
-                f.in_prev = seg + (size_t)(n0 - lo) * L;         // slot n0     = P_{n0-1}
-                f.in_cur = seg + (size_t)(n0 - lo + 1) * L;      // slot n0 + 1 = P_{n0}
-                if (p->wide) launch_fwd_w(f.nsteps, p->fwd_gen, (p->Wp & 1) == 0, grid, cs, f);
-                else launch_fwd(Tf, p->fwd_gen, grid, cs, f);
-            }
-            a.hbase = lo;
-            for (int k0 = hi; k0 > lo; k0 -= Ta, ++i) {          // adjoint steps k = hi .. lo + 1: slots lo + 1 .. hi
-                a.k0 = k0;
-                a.nsteps = std::min(Ta, k0 - lo);
-                const dim3 grid(geometry(c, a.nsteps));
-                for (int t = 0; t < ADJ_W_MAX; ++t) a.w[t] = t < a.nsteps ? p->wavf[k0 - 1 - t] : 0.0f;
-                const int pin = i & 1, pout = pin ^ 1;
-                a.in_l1 = ring + (size_t)(2 * pin) * L;
-                a.in_l2 = ring + (size_t)(2 * pin + 1) * L;
-                a.out_l1 = ring + (size_t)(2 * pout) * L;
-                a.out_l2 = ring + (size_t)(2 * pout + 1) * L;
-                if (p->wide) launch_adj_w(a.nsteps, (p->Wp & 1) == 0, !p->adj_tw_fma, grid, cs, a);
-                else launch_adj(Ta, grid, cs, a);
-            }
+    for (const Launch &l : sched) {
+        const hipStream_t cs = l.chain == 0 ? st : p->aux[l.chain - 1];
+        if (l.kind == Launch::levels) {
+            const size_t run = (size_t)l.ns_sh * slice;
+            const unsigned gx = (unsigned)std::min<size_t>((run + 255) / 256, 1024);
+            hipLaunchKernelGGL(k_ckpt_levels, dim3(gx, 2 * B), dim3(256), 0, cs, level(l.in, 0), level(l.out, 0), L,
+                               (size_t)ns * slice, (size_t)l.s_off * slice, run, B);
+        } else if (l.kind == Launch::fwd) {
+            f.g.s_off = l.s_off; f.g.ns_grp = l.ns_grp; f.g.tiles_x = l.tiles_x; f.g.ntiles = l.ntiles;
+            f.ns_sh = l.ns_sh; f.spw = l.spw;
+            f.n0 = l.first; f.nsteps = l.nsteps; f.hbase = l.hbase;
+            for (int t = 0; t < FWD_W_MAX; ++t) f.w[t] = t < l.nsteps ? p->wavf[l.first + t] : 0.0f;
+            f.in_prev = level(l.in, 0); f.in_cur = level(l.in, 1);
+            f.out_prev = level(l.out, 0); f.out_cur = level(l.out, 1);
+            launch_kernel(chunk_fwd_kernel(p, l.nsteps), l.grid, cs, f);
+        } else {
+            a.g.s_off = l.s_off; a.g.ns_grp = l.ns_grp; a.g.tiles_x = l.tiles_x; a.g.ntiles = l.ntiles;
+            a.ns_sh = l.ns_sh; a.spw = l.spw;
+            a.k0 = l.first; a.nsteps = l.nsteps; a.hbase = l.hbase;
+            for (int t = 0; t < ADJ_W_MAX; ++t) a.w[t] = t < l.nsteps ? p->wavf[l.first - 1 - t] : 0.0f;
+            a.in_l1 = level(l.in, 0); a.in_l2 = level(l.in, 1);
+            a.out_l1 = level(l.out, 0); a.out_l2 = level(l.out, 1);
+            launch_kernel(chunk_adj_kernel(p, l.nsteps), l.grid, cs, a);
         }
     }
     RDQ_CHECK(hipGetLastError());
@@ -3638,6 +3475,29 @@ void drop_graphs(rdq_fwi_plan *p)
     (void)hipDeviceSynchronize();
     for (auto &e : p->cache) (void)hipGraphExecDestroy(e.exec);
     p->cache.clear();
+}
+
+// A setting that shapes the launches (cached graphs encode them): changing it drops the graphs.
+// Caller holds p->mu.
+template <class T>
+void set_knob(rdq_fwi_plan *p, T &knob, T value)
+{
+    if (knob != value) drop_graphs(p);
+    knob = value;
+}
+
+// Several receivers in one padded column: their residuals folded per column into the ring's tail
+// (k_rcv_fold), which the adjoint kernels then read in place of the caller's dseis.
+int fold_residuals(const rdq_fwi_plan *p, int B, const float *&dseis, float *ring, hipStream_t st)
+{
+    if (!p->rmulti) return 0;
+    float *fold = ring + 8 * (size_t)B * p->g.ns * p->Hp * p->ld;
+    const size_t rows = (size_t)B * p->g.ns * p->nrec, n = rows * p->ncolr;
+    hipLaunchKernelGGL(k_rcv_fold, dim3((unsigned)std::min<size_t>((n + 255) / 256, 4096)), dim3(256), 0, st,
+                       dseis, fold, p->d_colx, p->d_rcv_start, p->d_rcv_list, p->g.ng, p->ncolr, rows);
+    RDQ_CHECK(hipGetLastError());
+    dseis = fold;
+    return 0;
 }
 
 template <class F>
@@ -3794,13 +3654,9 @@ int rdq_fwi_set_tuning(rdq_fwi_plan *p, int32_t fwd_steps, int32_t adj_steps, in
         chains > 16)
         return RDQ_E_INVALID;
     std::lock_guard<std::mutex> lk(p->mu);
-    if (p->fwd_T != fwd_steps || p->adj_T != adj_steps || p->chains != chains) {   // graphs encode these
-        drop_graphs(p);
-        p->cache.clear();
-    }
-    p->fwd_T = fwd_steps;
-    p->adj_T = adj_steps;
-    p->chains = chains;
+    set_knob(p, p->fwd_T, fwd_steps);
+    set_knob(p, p->adj_T, adj_steps);
+    set_knob(p, p->chains, chains);
     return 0;
 }
 
@@ -3808,11 +3664,7 @@ int rdq_fwi_set_wide_fwd_steps(rdq_fwi_plan *p, int32_t steps)
 {
     if (!p || steps < 0 || steps > TW_FWD_MAXT) return RDQ_E_INVALID;   // 0 = set_tuning's fwd_steps
     std::lock_guard<std::mutex> lk(p->mu);
-    if (p->fwd_Tw != steps) {   // graphs encode the launch sequence
-        drop_graphs(p);
-        p->cache.clear();
-    }
-    p->fwd_Tw = steps;
+    set_knob(p, p->fwd_Tw, steps);
     return 0;
 }
 
@@ -3820,11 +3672,7 @@ int rdq_fwi_set_wide_fwd_shots(rdq_fwi_plan *p, int32_t shots)
 {
     if (!p || shots < 0 || shots > 64) return RDQ_E_INVALID;   // 0 = auto (wide_spw)
     std::lock_guard<std::mutex> lk(p->mu);
-    if (p->fwd_spw != shots) {   // graphs encode the grids
-        drop_graphs(p);
-        p->cache.clear();
-    }
-    p->fwd_spw = shots;
+    set_knob(p, p->fwd_spw, shots);
     return 0;
 }
 
@@ -3832,11 +3680,7 @@ int rdq_fwi_set_wide_adj_shots(rdq_fwi_plan *p, int32_t shots)
 {
     if (!p || shots < 0 || shots > 64) return RDQ_E_INVALID;   // 0 = auto (wide_spw)
     std::lock_guard<std::mutex> lk(p->mu);
-    if (p->adj_spw != shots) {   // graphs encode the grids
-        drop_graphs(p);
-        p->cache.clear();
-    }
-    p->adj_spw = shots;
+    set_knob(p, p->adj_spw, shots);
     return 0;
 }
 
@@ -3844,11 +3688,7 @@ int rdq_fwi_set_wide_adj_steps(rdq_fwi_plan *p, int32_t steps)
 {
     if (!p || steps < 0 || steps > TW_ADJ_MAXT) return RDQ_E_INVALID;   // 0 = auto (wide_adj_depth)
     std::lock_guard<std::mutex> lk(p->mu);
-    if (wide_adj_depth(p) != (steps ? steps : TW_ADJ_DEFAULT)) {   // graphs encode the launch sequence
-        drop_graphs(p);
-        p->cache.clear();
-    }
-    p->adj_Tw = steps;
+    set_knob(p, p->adj_Tw, steps);
     return 0;
 }
 
@@ -3862,15 +3702,11 @@ int rdq_fwi_set_variant(rdq_fwi_plan *p, int32_t flags)
                        recurrence_ok(p);
     const int xcd = (flags & RDQ_VARIANT_NO_XCD_LOCAL) ? 0 : 1;
     const bool wide = (flags & RDQ_VARIANT_NARROW_CHUNKED) == 0;
-    if (p->fwd_gen != gen || p->adj_fma != fma || p->adj_tw_fma != twfma || p->xcd_mode != xcd || p->wide != wide) {
-        drop_graphs(p);
-        p->cache.clear();
-    }
-    p->fwd_gen = gen;
-    p->adj_fma = fma;
-    p->adj_tw_fma = twfma;
-    p->xcd_mode = xcd;
-    p->wide = wide;
+    set_knob(p, p->fwd_gen, gen);
+    set_knob(p, p->adj_fma, fma);
+    set_knob(p, p->adj_tw_fma, twfma);
+    set_knob(p, p->xcd_mode, xcd);
+    set_knob(p, p->wide, wide);
     return 0;
 }
 
@@ -3880,23 +3716,15 @@ int rdq_fwi_set_rows_per_wave(rdq_fwi_plan *p, int32_t fwd_rows, int32_t adj_row
         (adj_rows != 6 && adj_rows != 8 && adj_rows != 12))
         return RDQ_E_INVALID;
     std::lock_guard<std::mutex> lk(p->mu);
-    if (p->fwd_rw != fwd_rows || p->adj_rw != adj_rows) {
-        drop_graphs(p);
-        p->cache.clear();
-    }
-    p->fwd_rw = fwd_rows;
-    p->adj_rw = adj_rows;
+    set_knob(p, p->fwd_rw, fwd_rows);
+    set_knob(p, p->adj_rw, adj_rows);
     return 0;
 }
 int rdq_fwi_set_persistent(rdq_fwi_plan *p, int32_t mode)
 {
     if (!p || (mode != 0 && mode != 1 && mode != 8 && mode != 12 && mode != 16 && mode != -1)) return RDQ_E_INVALID;
     std::lock_guard<std::mutex> lk(p->mu);
-    if (p->persist != mode) {
-        drop_graphs(p);
-        p->cache.clear();
-    }
-    p->persist = mode;
+    set_knob(p, p->persist, mode);
     return 0;
 }
 
@@ -3907,13 +3735,13 @@ int rdq_fwi_launch_info(rdq_fwi_plan *p, int32_t B, int32_t out[6])
     int perf = 0, pera = 0;
     out[0] = persistent_nw(p, B, false, &perf);
     out[1] = persistent_nw(p, B, true, &pera);
-    const int fwdT = !out[0] && p->wide ? wide_fwd_depth(p) : p->fwd_T;   // chunked forward: the wide kernels' depth
-    out[2] = fwdT;
-    const int adjT = !out[1] && p->wide ? wide_adj_depth(p) : p->adj_T;   // chunked adjoint: the wide kernels' depth
-    out[3] = adjT;
-    const int ns = B * p->g.ns, nt = p->g.nt;   // persistent: one launch per slice group
-    out[4] = out[0] ? (ns + perf - 1) / perf : (nt + fwdT - 1) / fwdT;
-    out[5] = out[1] ? (ns + pera - 1) / pera : (nt + adjT - 1) / adjT;
+    out[2] = out[0] ? p->fwd_T : chunk_depth(p, false);   // chunked: the wide kernels' depth
+    out[3] = out[1] ? p->adj_T : chunk_depth(p, true);
+    // persistent: one launch per slice group; chunked: the store-all schedule's launches per chain
+    const int ns = B * p->g.ns;
+    const CkptPlan all = ckpt_plan(p, p->g.nt);
+    out[4] = out[0] ? (ns + perf - 1) / perf : count_launches(chunked_schedule(p, B, Pass::fwd_ring, all), Launch::fwd);
+    out[5] = out[1] ? (ns + pera - 1) / pera : count_launches(chunked_schedule(p, B, Pass::adj_hist, all), Launch::adj);
     return 0;
 }
 
@@ -3930,12 +3758,14 @@ int rdq_fwi_wide_info(rdq_fwi_plan *p, int32_t B, int32_t out[4])
 {
     if (!p || !out || B < 1) return RDQ_E_INVALID;
     std::lock_guard<std::mutex> lk(p->mu);
-    const int S = chain_count(p), ns0 = p->g.ns / S;   // chain 0: shots [0, ns / S), the smallest group
-    const int Tf = wide_fwd_depth(p), Ta = wide_adj_depth(p);
-    out[0] = S;
-    out[1] = p->wide ? wide_spw(p->fwd_spw, B * tw_tiles_x(p->Wp, Tf) * tw_tiles_y(p->Hp, Tf, false), ns0, false, S) : 1;
-    out[2] = p->wide ? wide_spw(p->adj_spw, B * tw_tiles_x(p->Wp, Ta) * tw_tiles_y(p->Hp, Ta, true), ns0, true, S) : 1;
-    out[3] = ns0;
+    // the first launch of chain 0 (shots [0, ns / S), the smallest group) of the store-all schedules
+    const CkptPlan all = ckpt_plan(p, p->g.nt);
+    const Launch f = chunked_schedule(p, B, Pass::fwd_ring, all).front();
+    const Launch a = chunked_schedule(p, B, Pass::adj_hist, all).front();
+    out[0] = chain_count(p);
+    out[1] = f.spw;
+    out[2] = a.spw;
+    out[3] = f.ns_sh;
     return 0;
 }
 
@@ -3944,7 +3774,6 @@ int rdq_fwi_set_profile(rdq_fwi_plan *p, int32_t enable)
     if (!p) return RDQ_E_INVALID;
     std::lock_guard<std::mutex> lk(p->mu);
     drop_graphs(p);   // graphs bake the pointer in
-    p->cache.clear();
     if (enable && !p->d_prof) {
         RDQ_CHECK(hipMalloc(&p->d_prof, 2 * PROF_WORDS * sizeof(unsigned long long)));
         RDQ_CHECK(hipMemset(p->d_prof, 0, 2 * PROF_WORDS * sizeof(unsigned long long)));
@@ -3998,11 +3827,7 @@ int rdq_fwi_set_status_buffer(rdq_fwi_plan *p, uint32_t *words)
 {
     if (!p) return RDQ_E_INVALID;
     std::lock_guard<std::mutex> lk(p->mu);
-    if (p->d_status != (words ? words : p->d_status_own)) {
-        drop_graphs(p);
-        p->cache.clear();
-    }
-    p->d_status = words ? words : p->d_status_own;
+    set_knob(p, p->d_status, words ? words : p->d_status_own);
     return 0;
 }
 
@@ -4085,8 +3910,12 @@ int rdq_fwi_forward(const rdq_fwi_plan *pc, int32_t B, const float *coeffs, floa
         // arrival counters of pt_assign are zeroed by a stream-ordered memset right before it)
         return launch_forward_pt(p, B, nw, per, coeffs, seis, hist, ring, st);
     }
-    return run_cached(p, hist ? 0 : 1, B, {coeffs, seis, hist, ring}, st,
-                      [&](hipStream_t s) { return launch_forward(p, B, coeffs, seis, hist, ring, s); });
+    // chunked: the store-all schedule, writing the history or (no-grad) ping-ponging in the ring
+    ChunkBufs b{};
+    b.coeffs = coeffs; b.seis = seis; b.hist = hist; b.ring = ring;
+    return run_cached(p, hist ? 0 : 1, B, {coeffs, seis, hist, ring}, st, [&](hipStream_t s) {
+        return enqueue_chunked(p, B, hist ? Pass::fwd_hist : Pass::fwd_ring, p->g.nt, b, s);
+    });
 }
 
 int rdq_fwi_adjoint(const rdq_fwi_plan *pc, int32_t B, const float *coeffs, const float *hist,
@@ -4096,20 +3925,15 @@ int rdq_fwi_adjoint(const rdq_fwi_plan *pc, int32_t B, const float *coeffs, cons
     if (!p || !coeffs || !hist || !dseis || !ring || !gA || !gk || !gbeta || B < 1) return RDQ_E_INVALID;
     std::lock_guard<std::mutex> lk(p->mu);
     RDQ_TRY(plan_enter(p, st));
-    if (p->rmulti) {   // several receivers in a column: fold the residuals per column (ring tail)
-        float *fold = ring + 8 * (size_t)B * p->g.ns * p->Hp * p->ld;
-        const size_t rows = (size_t)B * p->g.ns * p->nrec, n = rows * p->ncolr;
-        hipLaunchKernelGGL(k_rcv_fold, dim3((unsigned)std::min<size_t>((n + 255) / 256, 4096)), dim3(256), 0, st,
-                           dseis, fold, p->d_colx, p->d_rcv_start, p->d_rcv_list, p->g.ng, p->ncolr, rows);
-        RDQ_CHECK(hipGetLastError());
-        dseis = fold;
-    }
+    RDQ_TRY(fold_residuals(p, B, dseis, ring, st));
     int per = 0;
     if (const int nw = persistent_nw(p, B, true, &per))
         return launch_adjoint_pt(p, B, nw, per, coeffs, hist, dseis, ring, gA, gk, gbeta, st);
-    return run_cached(p, 2, B, {coeffs, hist, dseis, ring, gA, gk, gbeta}, st, [&](hipStream_t s) {
-        return launch_adjoint(p, B, coeffs, hist, dseis, ring, gA, gk, gbeta, s);
-    });
+    ChunkBufs b{};
+    b.coeffs = coeffs; b.hist = const_cast<float *>(hist); b.ring = ring; b.dseis = dseis;
+    b.gA = gA; b.gk = gk; b.gbeta = gbeta;
+    return run_cached(p, 2, B, {coeffs, hist, dseis, ring, gA, gk, gbeta}, st,
+                      [&](hipStream_t s) { return enqueue_chunked(p, B, Pass::adj_hist, p->g.nt, b, s); });
 }
 
 int rdq_fwi_ckpt_sizes(const rdq_fwi_plan *p, int32_t B, int32_t K, rdq_fwi_ckpt_sizes_t *o)
@@ -4129,17 +3953,11 @@ int rdq_fwi_ckpt_info(rdq_fwi_plan *p, int32_t B, int32_t K, int32_t out[4])
     if (!p || !out || B < 1 || K < 1) return RDQ_E_INVALID;
     std::lock_guard<std::mutex> lk(p->mu);
     const CkptPlan cp = ckpt_plan(p, K);
-    const int Tf = p->wide ? wide_fwd_depth(p) : p->fwd_T, Ta = p->wide ? wide_adj_depth(p) : p->adj_T;
-    int nf = 0, na = 0;
-    for (int sg = 0; sg < cp.nseg; ++sg) {
-        const int len = cp.hi(sg) - cp.lo(sg);
-        nf += (len + Tf - 1) / Tf;
-        na += (len + Ta - 1) / Ta;
-    }
+    const std::vector<Launch> bwd = chunked_schedule(p, B, Pass::adj_ckpt, cp);
     out[0] = 0;            // the first pass runs the chunked kernels
     out[1] = cp.nseg;
-    out[2] = nf;
-    out[3] = nf + na;      // every segment: its recompute, then its adjoint
+    out[2] = count_launches(chunked_schedule(p, B, Pass::fwd_ring, cp), Launch::fwd);
+    out[3] = count_launches(bwd, Launch::fwd) + count_launches(bwd, Launch::adj);   // every segment: its recompute, then its adjoint
     return 0;
 }
 
@@ -4151,9 +3969,10 @@ int rdq_fwi_forward_ckpt(const rdq_fwi_plan *pc, int32_t B, int32_t K, const flo
     if (!ckpt && ckpt_plan(p, K).nseg > 1) return RDQ_E_INVALID;
     std::lock_guard<std::mutex> lk(p->mu);
     RDQ_TRY(plan_enter(p, st));
+    ChunkBufs b{};
+    b.coeffs = coeffs; b.seis = seis; b.ckpt = ckpt; b.ring = ring;
     return run_cached(p, 3, B, {coeffs, seis, ckpt, ring}, st,
-                      [&](hipStream_t s) { return launch_forward_ckpt(p, B, K, coeffs, seis, ckpt, ring, s); },
-                      ckpt_plan(p, K).K);
+                      [&](hipStream_t s) { return enqueue_chunked(p, B, Pass::fwd_ring, K, b, s); }, ckpt_plan(p, K).K);
 }
 
 int rdq_fwi_adjoint_ckpt(const rdq_fwi_plan *pc, int32_t B, int32_t K, const float *coeffs, const float *ckpt,
@@ -4165,17 +3984,12 @@ int rdq_fwi_adjoint_ckpt(const rdq_fwi_plan *pc, int32_t B, int32_t K, const flo
     if (!ckpt && ckpt_plan(p, K).nseg > 1) return RDQ_E_INVALID;
     std::lock_guard<std::mutex> lk(p->mu);
     RDQ_TRY(plan_enter(p, st));
-    if (p->rmulti) {   // several receivers in a column: fold the residuals per column (ring tail), as rdq_fwi_adjoint
-        float *fold = ring + 8 * (size_t)B * p->g.ns * p->Hp * p->ld;
-        const size_t rows = (size_t)B * p->g.ns * p->nrec, n = rows * p->ncolr;
-        hipLaunchKernelGGL(k_rcv_fold, dim3((unsigned)std::min<size_t>((n + 255) / 256, 4096)), dim3(256), 0, st,
-                           dseis, fold, p->d_colx, p->d_rcv_start, p->d_rcv_list, p->g.ng, p->ncolr, rows);
-        RDQ_CHECK(hipGetLastError());
-        dseis = fold;
-    }
-    return run_cached(p, 4, B, {coeffs, ckpt, seg, dseis, ring, gA, gk, gbeta}, st, [&](hipStream_t s) {
-        return launch_adjoint_ckpt(p, B, K, coeffs, ckpt, seg, dseis, ring, gA, gk, gbeta, s);
-    }, ckpt_plan(p, K).K);
+    RDQ_TRY(fold_residuals(p, B, dseis, ring, st));
+    ChunkBufs b{};
+    b.coeffs = coeffs; b.hist = seg; b.ckpt = const_cast<float *>(ckpt); b.ring = ring; b.dseis = dseis;
+    b.gA = gA; b.gk = gk; b.gbeta = gbeta;
+    return run_cached(p, 4, B, {coeffs, ckpt, seg, dseis, ring, gA, gk, gbeta}, st,
+                      [&](hipStream_t s) { return enqueue_chunked(p, B, Pass::adj_ckpt, K, b, s); }, ckpt_plan(p, K).K);
 }
 
 int rdq_fwi_grad_finalize(const rdq_fwi_plan *p, int32_t B, const float *coeffs, const void *vstat,
