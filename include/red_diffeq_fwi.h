@@ -146,6 +146,16 @@ int rdq_fwi_set_rows_per_wave(rdq_fwi_plan *plan, int32_t fwd_rows, int32_t adj_
  * the one that would; configs[1] forward 1.210 -> 1.196 ms against 0.25 us; the barrier-free adjoint
  * is fastest without a delay).  Results are identical for every delay; only speed changes. */
 int rdq_fwi_set_sweep_delay(rdq_fwi_plan *plan, int32_t fwd_ticks, int32_t adj_ticks);
+/* What a persistent launch overlaps with the round trip of its per-epoch hand-off sweep, for the forward
+ * and the (recurrence) adjoint; 0 = nothing (sweep, then the post-sweep work):
+ *   adjoint 1 (default): the sweep's first pass is issued into registers of its own and the dead cells
+ *              (outside the next epoch's dependence cone) are zeroed while it is in flight, instead of
+ *              after the sweep on the path to the next step (configs[1]: 1.490 -> 1.458 ms);
+ *   forward:   0 only (RDQ_E_INVALID otherwise): no overlapped form of the forward measured faster.
+ * Mode 1 is built at 4 steps per epoch (the default depth); other depths and the exact-order adjoint run
+ * mode 0 (rdq_fwi_launch_info reports the mode that runs).  Only the order of independent register and
+ * memory operations differs: results are bit-identical in both modes. */
+int rdq_fwi_set_handoff_overlap(rdq_fwi_plan *plan, int32_t fwd_mode, int32_t adj_mode);
 /* 1 (default) = run each time loop as ONE persistent launch (regions resident in registers for
  * all nt steps, epoch-wise neighbour hand-offs) whenever the whole grid fits resident on the
  * device: small surveys (at most 200 workgroups, e.g. 3 OpenFWI shots) in 64 x 64 regions of 16
@@ -171,8 +181,9 @@ int rdq_fwi_set_status_buffer(rdq_fwi_plan *plan, uint32_t *words);
  * class (16 = 64 x 64 regions of 16 waves x 4 rows, 12 = 64 x 96 regions, 8 = 64 x 64 of 8 waves x 8
  * rows; 0 = chunked), the same for the adjoint, forward steps per epoch/launch,
  * adjoint steps per epoch/launch, forward time-loop launches per call, adjoint time-loop launches
- * per call} (persistent: one per resident shot group; chunked: ceil(nt / T)). */
-int rdq_fwi_launch_info(rdq_fwi_plan *plan, int32_t B, int32_t out[6]);
+ * per call (persistent: one per resident shot group; chunked: ceil(nt / T)), the hand-off overlap mode
+ * the forward runs, the same for the adjoint (rdq_fwi_set_handoff_overlap; 0 for chunked launches)}. */
+int rdq_fwi_launch_info(rdq_fwi_plan *plan, int32_t B, int32_t out[8]);
 /* The wide chunked kernels' launch shape for batch B: out = {concurrent launch chains, shots per
  * workgroup of the forward's and of the adjoint's full-depth launches of chain 0 (the automatic choice
  * unless rdq_fwi_set_wide_*_shots fixed one), shots in chain 0}. */
@@ -186,6 +197,17 @@ int rdq_fwi_read_profile(rdq_fwi_plan *plan, uint64_t out[12]);
 /* Per-wave records of the last read_profile: out[(block * 16 + wave) * 3 + {0,1,2}] = {hand-off,
  * steps, publish} ticks of the forward (adj = 0) or adjoint (adj = 1) kernel. */
 int rdq_fwi_profile_waves(rdq_fwi_plan *plan, int32_t adj, uint64_t *out, size_t count);
+/* The finer split of the last read_profile: out[0..4] forward, out[5..9] adjoint, each {a, b, c, d,
+ * gradient} ticks summed over waves.  The hand-off wait = a + b + c + d exactly: a = publish end to the
+ * first sweep pass's issue (delay, scalar loads), b = the first pass's round trip, c = later passes,
+ * d = after the sweep (dead-cell zeroing, deferred history stores, the next step's boundary rows, receiver
+ * records / next-epoch loads; also the launch prologue and the last epoch).  gradient = the adjoint's
+ * deferred gradient, which the publish figure of read_profile includes; publish - gradient = the granule
+ * stores' issue. */
+int rdq_fwi_profile_split(rdq_fwi_plan *plan, uint64_t out[10]);
+/* Per-wave records in full: out[(block * 16 + wave) * 8 + i], i = {hand-off, steps, publish, a, b, c, d,
+ * gradient} as above. */
+int rdq_fwi_profile_waves_split(rdq_fwi_plan *plan, int32_t adj, uint64_t *out, size_t count);
 
 /* Velocity input convention of rdq_fwi_coeffs / rdq_fwi_grad_finalize. */
 #define RDQ_VEL_NORMALIZED 0  /* v_norm in [-1,1], denormalised in-kernel: (v+1)/2*3000+1500 */

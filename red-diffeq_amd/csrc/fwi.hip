@@ -1225,9 +1225,10 @@ __global__ __launch_bounds__(64 * NW) void k_adj_tw(AdjTBArgs a)
 // zeroed before each launch; tag = epoch index (>= 1) so a zeroed granule never matches.
 constexpr int CP_SC1 = 16;                            // buffer cache policy: sc1 (write-through / L1 bypass)
 constexpr int PT_ADJ_SG = 8;                          // adjoint hand-off sweep: rows per load group
-constexpr size_t PROF_RAW = 8;                        // per-wave records after the 4 summary words
+constexpr size_t PROF_RAW = 16;                       // per-wave records after the 11 summary words (PT_PROF_FLUSH)
+constexpr size_t PROF_REC = 8;                        // words per wave record
 constexpr size_t PROF_WAVES = 4096 * 16;              // blocks x waves recorded
-constexpr size_t PROF_WORDS = PROF_RAW + PROF_WAVES * 3;   // per kernel (fwd, then adj)
+constexpr size_t PROF_WORDS = PROF_RAW + PROF_WAVES * PROF_REC;   // per kernel (fwd, then adj)
 constexpr unsigned long long PT_TIMEOUT_TICKS = 20000000ull;   // 200 ms of s_memrealtime (100 MHz)
 
 typedef unsigned int u32x2 __attribute__((ext_vector_type(2)));
@@ -1402,8 +1403,18 @@ __device__ PtTile pt_assign(const TBGeo &g, unsigned *status, int xcd_mode)
     {                                                                                               \
         unsigned long long t0_ = 0;                                                                 \
         const unsigned long long ts_ = prof ? __builtin_amdgcn_s_memrealtime() : 0;                 \
+        unsigned long long tb_ = ts_;                                                               \
+        if (prof) tsa += ts_ - tm;                                                                  \
         if constexpr (PT_PRIO) __builtin_amdgcn_s_setprio(PT_PRIO_WAIT);                            \
-        for (unsigned pass_ = 0; live; ++pass_) {                                                   \
+        PT_SWEEP_PASSES(GR, TAG, V0, V1, SG, 0)                                                     \
+        if (prof) { tlast = __builtin_amdgcn_s_memrealtime(); tsc += tlast - tb_; }                 \
+        if constexpr (PT_PRIO) __builtin_amdgcn_s_setprio(PT_PRIO_SWEPT);                           \
+        PT_SWEEP_ZERO(V0, V1)                                                                       \
+    }
+// the sweep's passes from pass number P0 on, until every halo granule carries TAG (or the wave gave up)
+#define PT_SWEEP_PASSES(GR, TAG, V0, V1, SG, P0)                                                    \
+    {                                                                                               \
+        for (unsigned pass_ = (P0); live; ++pass_) {                                                \
             /* the loads of a group of SG rows are all issued before any is checked: lanes        \
                without a halo cell in a row load from an out-of-range offset (no memory access,   \
                returns 0) instead of branching, which would make the compiler wait vmcnt(0) after \
@@ -1432,7 +1443,7 @@ __device__ PtTile pt_assign(const TBGeo &g, unsigned *status, int xcd_mode)
                 }                                                                                   \
             }                                                                                       \
             const bool done_ = __all(ok_);                                                          \
-            if (prof && pass_ == 0) tfp += __builtin_amdgcn_s_memrealtime() - ts_;                   \
+            if (prof && pass_ == 0) { tb_ = __builtin_amdgcn_s_memrealtime(); tfp += tb_ - ts_; tsb += tb_ - ts_; } \
             if (done_) { npass += pass_ + 1; break; }                                               \
             if (pass_ == 0) t0_ = __builtin_amdgcn_s_memrealtime();                                 \
             if ((pass_ & 15) == 15) {                                                               \
@@ -1449,7 +1460,9 @@ __device__ PtTile pt_assign(const TBGeo &g, unsigned *status, int xcd_mode)
             }                                                                                       \
             __builtin_amdgcn_s_sleep(1);                                                            \
         }                                                                                           \
-        if constexpr (PT_PRIO) __builtin_amdgcn_s_setprio(PT_PRIO_SWEPT);                           \
+    }
+#define PT_SWEEP_ZERO(V0, V1)                                                                       \
+    {                                                                                               \
         /* cells outside the next epoch's dependence cone: zeroed (bounded garbage) */             \
         unsigned rin_ = rin, rcy_ = rcy;                                                            \
         LAUNDER(rin_); LAUNDER(rcy_);                                                               \
@@ -1459,6 +1472,89 @@ __device__ PtTile pt_assign(const TBGeo &g, unsigned *status, int xcd_mode)
             PT_AT(V0, r) = keep_ ? PT_AT(V0, r) : 0.0f;                                             \
             PT_AT(V1, r) = keep_ ? PT_AT(V1, r) : 0.0f;                                             \
         }                                                                                           \
+    }
+// The same zeroing in fewer instructions (PT_SWEEP_SHADOW).  PT_SWEEP_ZERO compiles to 7 VALU per row: the
+// keep mask is rebuilt from 0 / 1 lane values (three selects, an and, a compare) before the two selects
+// that zero.  Here the lane's classes are one word (bit 0 keep_in, bit 1 cx) tested against the row's
+// scalar class: and, compare, two selects.  Same cells, same values.  (After the sweep, in the forward, it
+// changes nothing: 1.0101 -> 1.0102 ms, profiles/r9/kernel_ab_lean_zeroing.jsonl.)
+#define PT_SWEEP_ZERO_LEAN(V0, V1)                                                                  \
+    {                                                                                               \
+        unsigned rin_ = rin, rcy_ = rcy;                                                            \
+        LAUNDER(rin_); LAUNDER(rcy_);                                                               \
+        const unsigned kc_ = (keep_in ? 1u : 0u) | (cx ? 2u : 0u);                                  \
+        _Pragma("unroll") for (int r = 0; r < R; ++r) {                                             \
+            const unsigned sel_ = ((rin_ >> r) & 1u) ? 1u : (((rcy_ >> r) & 1u) ? 2u : 0u);         \
+            const bool keep_ = (kc_ & sel_) != 0u;                                                  \
+            PT_AT(V0, r) = keep_ ? PT_AT(V0, r) : 0.0f;                                             \
+            PT_AT(V1, r) = keep_ ? PT_AT(V1, r) : 0.0f;                                             \
+        }                                                                                           \
+    }
+
+// Hand-off overlap (rdq_fwi_set_handoff_overlap), PT_SWEEP_SHADOW: PT_SWEEP with the dead-cell zeroing
+// moved from after the sweep (where all of a SIMD's waves run it at once, on the path to the next step)
+// into the first pass's round trip.  The dead cells (not `keep_`) and the halo cells a pass reloads
+// (`nd_`) are disjoint sets fixed by the region's masks, so the cells hold the same values at the next
+// step whichever comes first.  The first pass's loads of rows 0 .. EN-1 are issued by PT_SWEEP_EARLY
+// into registers of their own, XE; then the zeroing; PT_SWEEP_OV issues the rows past EN, checks and
+// merges that first pass, and on a stale tag goes on with PT_SWEEP's passes unchanged (same bounded spin,
+// status word and `live`).  The compiler barrier keeps the loads ahead of the zeroing, and the register
+// pins keep the zeroing ahead of the wait for them.  tei: profile stamp of the first pass's issue.
+#define PT_SWEEP_SHADOW(GR, TAG, V0, V1, SG, EN)                                                    \
+    {                                                                                               \
+        u32x4 xe_[(EN)];                                                                            \
+        unsigned long long tei = 0;                                                                 \
+        PT_SWEEP_EARLY(GR, xe_, EN)                                                                 \
+        PT_SWEEP_ZERO_LEAN(V0, V1)                                                                  \
+        _Pragma("unroll") for (int i_ = 0; i_ < RP; ++i_) asm volatile("" : "+v"(V0[i_]), "+v"(V1[i_])); \
+        PT_SWEEP_OV(GR, TAG, V0, V1, SG, xe_, EN)                                                   \
+    }
+#define PT_SWEEP_ROW_OFS(r) ((((rin_) >> (r)) & 1u) ? vo_hx : ((((rcy_) >> (r)) & 1u) ? vo_cx : OOB))
+#define PT_SWEEP_EARLY(GR, XE, EN)                                                                  \
+    {                                                                                               \
+        if (prof) { tei = __builtin_amdgcn_s_memrealtime(); tsa += tei - tm; }                      \
+        unsigned rin_ = rin, rcy_ = rcy;                                                            \
+        LAUNDER(rin_); LAUNDER(rcy_);                                                               \
+        _Pragma("unroll") for (int r = 0; r < (EN); ++r)                                            \
+            XE[r] = gran_get(GR, PT_SWEEP_ROW_OFS(r), PT_ROFS(r) * 16);                             \
+        asm volatile("" ::: "memory");                                                              \
+    }
+#define PT_SWEEP_MERGE(X, r, TAG, V0, V1)                                                           \
+    {                                                                                               \
+        const bool nd_ = PT_SWEEP_ROW_OFS(r) != OOB;                                                \
+        ok_ = ok_ && (!nd_ || ((X).y == (TAG) && (X).w == (TAG)));                                  \
+        PT_AT(V0, r) = nd_ ? __uint_as_float((X).x) : PT_AT(V0, r);                                 \
+        PT_AT(V1, r) = nd_ ? __uint_as_float((X).z) : PT_AT(V1, r);                                 \
+    }
+#define PT_SWEEP_OV(GR, TAG, V0, V1, SG, XE, EN)                                                    \
+    {                                                                                               \
+        constexpr int LN_ = R - (EN);                   /* rows of the first pass not issued early */ \
+        static_assert(LN_ >= 0 && LN_ <= (SG), "PT_SWEEP_OV: one load group after the early rows"); \
+        unsigned long long t0_ = 0;                                                                 \
+        const unsigned long long ts_ = tei;                                                         \
+        unsigned long long tb_ = tei;                                                               \
+        if constexpr (PT_PRIO) __builtin_amdgcn_s_setprio(PT_PRIO_WAIT);                            \
+        bool first_ = false;                                                                        \
+        if (live) {                                                                                 \
+            unsigned rin_ = rin, rcy_ = rcy;                                                        \
+            LAUNDER(rin_); LAUNDER(rcy_);                                                           \
+            bool ok_ = true;                                                                        \
+            u32x4 x_[LN_ > 0 ? LN_ : 1];                                                            \
+            _Pragma("unroll") for (int i_ = 0; i_ < LN_; ++i_)                                      \
+                x_[i_] = gran_get(GR, PT_SWEEP_ROW_OFS((EN) + i_), PT_ROFS((EN) + i_) * 16);        \
+            _Pragma("unroll") for (int r = 0; r < (EN); ++r) PT_SWEEP_MERGE(XE[r], r, TAG, V0, V1)  \
+            _Pragma("unroll") for (int i_ = 0; i_ < LN_; ++i_) PT_SWEEP_MERGE(x_[i_], (EN) + i_, TAG, V0, V1) \
+            first_ = __all(ok_);                                                                    \
+            if (prof) {                                                                             \
+                const unsigned long long now_ = __builtin_amdgcn_s_memrealtime();                   \
+                tfp += now_ - ts_; tsb += now_ - tb_; tb_ = now_;                                   \
+            }                                                                                       \
+            if (first_) npass += 1;                                                                 \
+            else { t0_ = __builtin_amdgcn_s_memrealtime(); __builtin_amdgcn_s_sleep(1); }           \
+        }                                                                                           \
+        if (!first_) PT_SWEEP_PASSES(GR, TAG, V0, V1, SG, 1)                                        \
+        if (prof) { tlast = __builtin_amdgcn_s_memrealtime(); tsc += tlast - tb_; }                 \
+        if constexpr (PT_PRIO) __builtin_amdgcn_s_setprio(PT_PRIO_SWEPT);                           \
     }
 
 // publish the own-interior border cells of two levels (rows: interior; lanes: the interior
@@ -1499,6 +1595,36 @@ __device__ PtTile pt_assign(const TBGeo &g, unsigned *status, int xcd_mode)
 
 #define PT_PROF(ACC)                                                                                \
     if (prof) { const unsigned long long now_ = __builtin_amdgcn_s_memrealtime(); ACC += now_ - tm; tm = now_; }
+// Phase counters of the profiled build (10 ns ticks).  tsw / tst / tpb: hand-off wait, steps, publish
+// (the granule stores' issue); tgr: the adjoint's deferred gradient.  The wait splits, with no tick lost
+// between them (tsw = tsa + tsb + tsc + tsd), into tsa: publish end -> first sweep pass issued (delay,
+// scalar loads), tsb: the first pass's round trip, tsc: later passes, tsd: after the sweep (dead-cell
+// zeroing, deferred history stores, xm_put, FWD_RECORD / ADJ_ISSUE) and whatever else the wait counter
+// took (launch prologue, last epoch).  tfp: first pass issue -> checked (= tsb unless work overlaps it).
+#define PT_PROF_VARS                                                                                \
+    unsigned long long tsw = 0, tst = 0, tpb = 0, tgr = 0, tm = prof ? __builtin_amdgcn_s_memrealtime() : 0; \
+    unsigned long long tsa = 0, tsb = 0, tsc = 0, tsd = 0, tlast = 0;                               \
+    unsigned long long tfp = 0, npass = 0;                /* first-pass latency, sweep passes */
+// the wait counter's stamp: its part since the sweep ended (or all of it, without a sweep) is the tail
+#define PT_PROF_TAIL                                                                                \
+    if (prof) {                                                                                     \
+        const unsigned long long now_ = __builtin_amdgcn_s_memrealtime();                           \
+        tsw += now_ - tm; tsd += now_ - (tlast ? tlast : tm);                                       \
+        tm = now_; tlast = 0;                                                                       \
+    }
+// summary words [0..10] and the wave's record {wait, steps, publish + gradient, a, b, c, d, gradient}
+#define PT_PROF_FLUSH                                                                               \
+    if (prof && lane == 0) {                                                                        \
+        atomicAdd(prof + 0, tsw); atomicAdd(prof + 1, tst); atomicAdd(prof + 2, tpb + tgr); atomicAdd(prof + 3, 1ull); \
+        atomicAdd(prof + 4, tfp); atomicAdd(prof + 5, npass);                                       \
+        atomicAdd(prof + 6, tsa); atomicAdd(prof + 7, tsb); atomicAdd(prof + 8, tsc); atomicAdd(prof + 9, tsd); \
+        atomicAdd(prof + 10, tgr);                                                                  \
+        if (blockIdx.x < PROF_WAVES / 16) {                                                         \
+            unsigned long long *raw = prof + PROF_RAW + ((size_t)blockIdx.x * 16 + w) * PROF_REC;   \
+            raw[0] = tsw; raw[1] = tst; raw[2] = tpb + tgr; raw[3] = tsa; raw[4] = tsb; raw[5] = tsc; \
+            raw[6] = tsd; raw[7] = tgr;                                                             \
+        }                                                                                           \
+    }
 
 // Re-materialise a wave-uniform value inside the time loop: stops the compiler from hoisting the
 // per-row compares on it out of the loop as live 64-bit lane masks (which spill to VGPR lanes and
@@ -1707,8 +1833,7 @@ __global__ __launch_bounds__(64 * NW) void k_fwd_pt(FwdPtArgs a)
     for (int r = 0; r < R; ++r) hv[r] = (((rin >> r) & 1u) && xin) ? (PT_ROFS(r) + gx) * 4 : OOB;
     const int nep = (a.nt + T - 1) / T;
     bool live = true;
-    unsigned long long tsw = 0, tst = 0, tpb = 0, tm = prof ? __builtin_amdgcn_s_memrealtime() : 0;
-    unsigned long long tfp = 0, npass = 0;                // profile: first-pass latency, sweep passes
+    PT_PROF_VARS
     // The next epoch's wavelet samples (FWD_ISSUE) are scalar loads issued right after the publish: the
     // source row's first step no longer waits for them behind the deferred history stores.
     float wv[T];
@@ -1723,7 +1848,7 @@ __global__ __launch_bounds__(64 * NW) void k_fwd_pt(FwdPtArgs a)
     for (int e = 0; e < nep; ++e) {
         const int n0 = e * T;
         const __amdgpu_buffer_rsrc_t HFe = rsrc_of(a.hist + (size_t)(n0 + 2) * L + so);   // FWD_HIST
-        PT_PROF(tsw)
+        PT_PROF_TAIL
 #pragma unroll
         for (int t = 0; t < T; ++t) {
             const int n = n0 + t;
@@ -1754,15 +1879,8 @@ __global__ __launch_bounds__(64 * NW) void k_fwd_pt(FwdPtArgs a)
     }
 #undef FWD_STEP_SEL
 #undef FWD_ISSUE
-    PT_PROF(tsw)
-    if (prof && lane == 0) {
-        atomicAdd(prof + 0, tsw); atomicAdd(prof + 1, tst); atomicAdd(prof + 2, tpb); atomicAdd(prof + 3, 1ull);
-        atomicAdd(prof + 4, tfp); atomicAdd(prof + 5, npass);
-        if (blockIdx.x < PROF_WAVES / 16) {
-            unsigned long long *raw = prof + PROF_RAW + ((size_t)blockIdx.x * 16 + w) * 3;   // per wave
-            raw[0] = tsw; raw[1] = tst; raw[2] = tpb;
-        }
-    }
+    PT_PROF_TAIL
+    PT_PROF_FLUSH
 }
 
 #undef FWD_HIST
@@ -1973,8 +2091,7 @@ __global__ __launch_bounds__(64 * NW) void k_adj_pt(AdjPtArgs a)
     }
     const int nep = (a.nt + T - 1) / T;
     bool live = true;
-    unsigned long long tsw = 0, tst = 0, tpb = 0, tm = prof ? __builtin_amdgcn_s_memrealtime() : 0;
-    unsigned long long tfp = 0, npass = 0;                // profile: first-pass latency, sweep passes
+    PT_PROF_VARS
     for (int e = 0; e < nep; ++e) {
         const int ke = a.nt - e * T;                      // first step k of this epoch
         const bool last = e + 1 == nep;
@@ -2000,26 +2117,20 @@ __global__ __launch_bounds__(64 * NW) void k_adj_pt(AdjPtArgs a)
             const unsigned tag = (unsigned)(e + 1);
             const __amdgpu_buffer_rsrc_t GR = rsrc_of(a.gran + (size_t)(2 * ((e + 1) & 1)) * L + 2 * so);
             PT_PUBLISH(GR, tag, L0, L1)
+            PT_PROF(tpb)
             ADJ_GRAD(L0, L1, PB, PHB, wv[T - 1])          // the deferred last step (no neighbour data)
             const int kn = ke - T;                        // first step k of the next epoch
-            PT_PROF(tpb)
+            PT_PROF(tgr)
             PT_SWEEP_DELAY()
             PT_SWEEP(GR, tag, L0, L1, PT_ADJ_SG)
             ADJ_ISSUE
-            PT_PROF(tsw)
+            PT_PROF_TAIL
         }
     }
 #undef DLOAD
 #undef ADJ_ISSUE
 #undef HIST_RSRC
-    if (prof && lane == 0) {
-        atomicAdd(prof + 0, tsw); atomicAdd(prof + 1, tst); atomicAdd(prof + 2, tpb); atomicAdd(prof + 3, 1ull);
-        atomicAdd(prof + 4, tfp); atomicAdd(prof + 5, npass);
-        if (blockIdx.x < PROF_WAVES / 16) {
-            unsigned long long *raw = prof + PROF_RAW + ((size_t)blockIdx.x * 16 + w) * 3;   // per wave
-            raw[0] = tsw; raw[1] = tst; raw[2] = tpb;
-        }
-    }
+    PT_PROF_FLUSH
     if (xin) {
 #pragma unroll
         for (int r = 0; r < R; ++r)
@@ -2138,7 +2249,13 @@ __global__ __launch_bounds__(64 * NW) void k_adj_pt(AdjPtArgs a)
         if (t + 1 < T || last) ADJR_GRAD(CUR, PRV, wv[t], P0, P1, P2)                               \
     }
 
-template <int T, int NW, int RW, bool PROF>
+// OV (rdq_fwi_set_handoff_overlap): 0 = PT_SWEEP; 1 = the dead cells are zeroed while the sweep's first
+// pass is in flight (PT_SWEEP_SHADOW), in the lean form: 1.4897 -> 1.4579 ms at configs[1], modes
+// alternated x9 (profiles/r9/kernel_ab_lean_zeroing.jsonl; with PT_SWEEP_ZERO's form in the round trip
+// 1.4911 -> 1.4722, kernel_ab_adj_shadow_fwd_xmfirst.jsonl).  In the forward the zeroing in the round
+// trip was slower (1.011 -> 1.035 ms: more stale first passes) and the lean form after the sweep no
+// faster, so the forward has the one order.
+template <int T, int NW, int RW, bool PROF, int OV = 0>
 __global__ __launch_bounds__(64 * NW) void k_adj_pr(AdjPtArgs a)
 {
     unsigned long long *const prof = PROF ? a.prof : nullptr;   // phase counters: profiled build only
@@ -2224,8 +2341,7 @@ __global__ __launch_bounds__(64 * NW) void k_adj_pr(AdjPtArgs a)
     }
     const int nep = (a.nt + T - 1) / T;
     bool live = true;
-    unsigned long long tsw = 0, tst = 0, tpb = 0, tm = prof ? __builtin_amdgcn_s_memrealtime() : 0;
-    unsigned long long tfp = 0, npass = 0;                // profile: first-pass latency, sweep passes
+    PT_PROF_VARS
     xm_init<NW>(xm, w, lane);                             // no flag matches a tag until written
     __syncthreads();
     xm_put<NW>(xm, 0, w, lane, 1u, f32x2{0.0f, 0.0f}, f32x2{0.0f, 0.0f});   // A L_{nt+1} = 0, step 0's tag
@@ -2258,15 +2374,17 @@ __global__ __launch_bounds__(64 * NW) void k_adj_pr(AdjPtArgs a)
             const unsigned tag = (unsigned)(e + 1);
             const __amdgpu_buffer_rsrc_t GR = rsrc_of(a.gran + (size_t)(2 * ((e + 1) & 1)) * L + 2 * so);
             PT_PUBLISH(GR, tag, L0, L1)
-            ADJR_GRAD(L0, L1, wv[T - 1], QW(0), QW(1), QW(2))   // the deferred last step (no neighbour data)
-            const int kn = ke - T;                        // first step k of the next epoch
             PT_PROF(tpb)
+            const int kn = ke - T;                        // first step k of the next epoch
+            ADJR_GRAD(L0, L1, wv[T - 1], QW(0), QW(1), QW(2))   // the deferred last step (no neighbour data)
+            PT_PROF(tgr)
             PT_SWEEP_DELAY()
-            PT_SWEEP(GR, tag, L0, L1, PT_ADJ_SG)
+            if constexpr (OV == 0) PT_SWEEP(GR, tag, L0, L1, PT_ADJ_SG)
+            else PT_SWEEP_SHADOW(GR, tag, L0, L1, PT_ADJ_SG, (PT_ADJ_SG < R ? PT_ADJ_SG : R))
             // the next step's boundary rows, with the halo cells the sweep reloaded
             xm_put<NW>(xm, (e + 1) * T & 1, w, lane, (unsigned)((e + 1) * T) + 1u, A[0] * L1[0], A[1] * L1[1]);
             ADJ_ISSUE
-            PT_PROF(tsw)
+            PT_PROF_TAIL
         }
         if constexpr ((T & 3) != 0) {   // restore Q0 = the next epoch's P_k
 #pragma unroll
@@ -2280,14 +2398,7 @@ __global__ __launch_bounds__(64 * NW) void k_adj_pr(AdjPtArgs a)
 #undef DLOAD
 #undef ADJ_ISSUE
 #undef HIST_RSRC
-    if (prof && lane == 0) {
-        atomicAdd(prof + 0, tsw); atomicAdd(prof + 1, tst); atomicAdd(prof + 2, tpb); atomicAdd(prof + 3, 1ull);
-        atomicAdd(prof + 4, tfp); atomicAdd(prof + 5, npass);
-        if (blockIdx.x < PROF_WAVES / 16) {
-            unsigned long long *raw = prof + PROF_RAW + ((size_t)blockIdx.x * 16 + w) * 3;   // per wave
-            raw[0] = tsw; raw[1] = tst; raw[2] = tpb;
-        }
-    }
+    PT_PROF_FLUSH
     double ksum = 0.0;                                    // gk = sum K * (sum_k P (L_{k+1} - L_k))
     if (xin) {
 #pragma unroll
@@ -2322,8 +2433,19 @@ __global__ __launch_bounds__(64 * NW) void k_adj_pr(AdjPtArgs a)
 #undef PAIR_VERT
 #undef PT_AT
 #undef PT_SWEEP
+#undef PT_SWEEP_PASSES
+#undef PT_SWEEP_ZERO
+#undef PT_SWEEP_ZERO_LEAN
+#undef PT_SWEEP_ROW_OFS
+#undef PT_SWEEP_EARLY
+#undef PT_SWEEP_MERGE
+#undef PT_SWEEP_OV
+#undef PT_SWEEP_SHADOW
 #undef PT_PUBLISH
 #undef PT_PROF
+#undef PT_PROF_VARS
+#undef PT_PROF_TAIL
+#undef PT_PROF_FLUSH
 #undef PT_SWEEP_DELAY
 #undef PT_ROFS
 #undef PT_REGION_INIT
@@ -2644,6 +2766,9 @@ struct GraphEntry {
 
 // default pre-sweep delays of the persistent forward / adjoint, 10 ns ticks (PT_SWEEP_DELAY)
 constexpr int RDQ_SWEEP_DELAY_FWD = 15, RDQ_SWEEP_DELAY_ADJ = 0;
+// default hand-off overlap mode of the persistent adjoint (rdq_fwi_set_handoff_overlap); mode 1 exists at
+// PT_OV_T steps per epoch
+constexpr int RDQ_OVERLAP_ADJ = 1, PT_OV_T = 4;
 
 struct rdq_fwi_plan {
     rdq_fwi_geom g;
@@ -2671,6 +2796,7 @@ struct rdq_fwi_plan {
                                   // adjoint 6: 1.649 vs 1.672 ms for 8, profiles/r3/adj_rows_nb_ab.txt)
     int fwd_T = 4, adj_T = 4;   // time steps per launch (temporal blocking depth), <= TB_MAXT
     int fwd_delay = RDQ_SWEEP_DELAY_FWD, adj_delay = RDQ_SWEEP_DELAY_ADJ;   // persistent kernels' pre-sweep delay (ticks)
+    int adj_ov = RDQ_OVERLAP_ADJ;   // the persistent (recurrence) adjoint's hand-off overlap mode
     int adj_Tw = 0;             // the wide chunked adjoint's depth (<= TW_ADJ_MAXT); 0 = auto, see wide_adj_depth
     int fwd_Tw = 0;             // the wide chunked forward's depth (<= TW_FWD_MAXT); 0 = auto, see wide_fwd_depth
     int adj_spw = 0;            // the wide chunked adjoint's shots per workgroup, 0 = auto (wide_spw)
@@ -2997,23 +3123,29 @@ KernelRef<FwdPtArgs> fwd_pt_kernel(const rdq_fwi_plan *p, int NW, int T, bool pr
 // The persistent adjoint: the FMA / recurrence build (k_adj_pr, the plan's rows per wave for 96-row
 // regions) or the oracle's exact operation order (k_adj_pt, 8 rows per wave: the 16-wave class of 64-row
 // regions pairs with its 8-wave kernel).
-template <int T, bool PROF>
+template <int T, bool PROF, int OV = 0>
 KernelRef<AdjPtArgs> adj_pt_T(int NW, int rw, bool fma)
 {
     if (!fma) {
         if (NW != 12) return {k_adj_pt<T, 8, PROF>, 64 * 8};
         return {k_adj_pt<T, 12, PROF>, 64 * 12};
     }
-    if (NW == 16) return {k_adj_pr<T, 16, 4, PROF>, 64 * 16};
-    if (NW != 12) return {k_adj_pr<T, 8, 8, PROF>, 64 * 8};
+    if (NW == 16) return {k_adj_pr<T, 16, 4, PROF, OV>, 64 * 16};
+    if (NW != 12) return {k_adj_pr<T, 8, 8, PROF, OV>, 64 * 8};
     switch (rw) {
-    case 12: return {k_adj_pr<T, 8, 12, PROF>, 64 * 8};
-    case 6: return {k_adj_pr<T, 16, 6, PROF>, 64 * 16};
-    default: return {k_adj_pr<T, 12, 8, PROF>, 64 * 12};
+    case 12: return {k_adj_pr<T, 8, 12, PROF, OV>, 64 * 8};
+    case 6: return {k_adj_pr<T, 16, 6, PROF, OV>, 64 * 16};
+    default: return {k_adj_pr<T, 12, 8, PROF, OV>, 64 * 12};
     }
 }
+// The hand-off overlap mode the persistent adjoint runs (0 = the plain order): mode 1 is built at PT_OV_T
+// steps per epoch, for the recurrence adjoint.
+int adj_overlap(const rdq_fwi_plan *p) { return p->adj_T == PT_OV_T && p->adj_fma ? p->adj_ov : 0; }
 KernelRef<AdjPtArgs> adj_pt_kernel(const rdq_fwi_plan *p, int NW, int T, bool fma, bool prof)
 {
+    static_assert(PT_OV_T == 4, "the profiled and the overlap builds share their depth");
+    if (T == 4 && fma && adj_overlap(p))
+        return prof ? adj_pt_T<4, true, 1>(NW, p->adj_rw, true) : adj_pt_T<4, false, 1>(NW, p->adj_rw, true);
     if (prof && T == 4) return adj_pt_T<4, true>(NW, p->adj_rw, fma);
     return with_depth<TB_MAXT>(T, [&](auto t) { return adj_pt_T<t(), false>(NW, p->adj_rw, fma); });
 }
@@ -3728,7 +3860,7 @@ int rdq_fwi_set_persistent(rdq_fwi_plan *p, int32_t mode)
     return 0;
 }
 
-int rdq_fwi_launch_info(rdq_fwi_plan *p, int32_t B, int32_t out[6])
+int rdq_fwi_launch_info(rdq_fwi_plan *p, int32_t B, int32_t out[8])
 {
     if (!p || !out || B < 1) return RDQ_E_INVALID;
     std::lock_guard<std::mutex> lk(p->mu);
@@ -3742,6 +3874,8 @@ int rdq_fwi_launch_info(rdq_fwi_plan *p, int32_t B, int32_t out[6])
     const CkptPlan all = ckpt_plan(p, p->g.nt);
     out[4] = out[0] ? (ns + perf - 1) / perf : count_launches(chunked_schedule(p, B, Pass::fwd_ring, all), Launch::fwd);
     out[5] = out[1] ? (ns + pera - 1) / pera : count_launches(chunked_schedule(p, B, Pass::adj_hist, all), Launch::adj);
+    out[6] = 0;   // the forward has the one order
+    out[7] = out[1] ? adj_overlap(p) : 0;
     return 0;
 }
 
@@ -3751,6 +3885,14 @@ int rdq_fwi_set_sweep_delay(rdq_fwi_plan *p, int32_t fwd_ticks, int32_t adj_tick
     std::lock_guard<std::mutex> lk(p->mu);
     p->fwd_delay = fwd_ticks;   // (persistent launches are direct, not graphs: nothing cached to drop)
     p->adj_delay = adj_ticks;
+    return 0;
+}
+
+int rdq_fwi_set_handoff_overlap(rdq_fwi_plan *p, int32_t fwd_mode, int32_t adj_mode)
+{
+    if (!p || fwd_mode != 0 || adj_mode < 0 || adj_mode > 1) return RDQ_E_INVALID;
+    std::lock_guard<std::mutex> lk(p->mu);
+    p->adj_ov = adj_mode;   // (persistent launches are direct, not graphs: nothing cached to drop)
     return 0;
 }
 
@@ -3798,11 +3940,32 @@ int rdq_fwi_read_profile(rdq_fwi_plan *p, uint64_t out[12])
     return 0;
 }
 
+int rdq_fwi_profile_split(rdq_fwi_plan *p, uint64_t out[10])
+{
+    if (!p || !out) return RDQ_E_INVALID;
+    std::lock_guard<std::mutex> lk(p->mu);
+    for (int i = 0; i < 5; ++i) {
+        out[i] = p->prof_host.empty() ? 0 : p->prof_host[6 + i];
+        out[5 + i] = p->prof_host.empty() ? 0 : p->prof_host[PROF_WORDS + 6 + i];
+    }
+    return 0;
+}
+
 int rdq_fwi_profile_waves(rdq_fwi_plan *p, int32_t adj, uint64_t *out, size_t count)
 {
     if (!p || !out || (adj != 0 && adj != 1)) return RDQ_E_INVALID;
     std::lock_guard<std::mutex> lk(p->mu);
     const size_t n = std::min(count, PROF_WAVES * 3);
+    for (size_t i = 0; i < n; ++i)   // the first three words of each wave's record
+        out[i] = p->prof_host.empty() ? 0 : p->prof_host[(adj ? PROF_WORDS : 0) + PROF_RAW + i / 3 * PROF_REC + i % 3];
+    return 0;
+}
+
+int rdq_fwi_profile_waves_split(rdq_fwi_plan *p, int32_t adj, uint64_t *out, size_t count)
+{
+    if (!p || !out || (adj != 0 && adj != 1)) return RDQ_E_INVALID;
+    std::lock_guard<std::mutex> lk(p->mu);
+    const size_t n = std::min(count, PROF_WAVES * PROF_REC);
     for (size_t i = 0; i < n; ++i)
         out[i] = p->prof_host.empty() ? 0 : p->prof_host[(adj ? PROF_WORDS : 0) + PROF_RAW + i];
     return 0;

@@ -157,18 +157,27 @@ class FwiPlan:
 
     def launch_info(self, B):
         """{'fwd_persistent', 'adj_persistent', 'fwd_class' / 'adj_class' (persistent region class: 16 /
-        12 / 8, 0 = chunked), 'fwd_T', 'adj_T', 'fwd_launches', 'adj_launches'} of a
+        12 / 8, 0 = chunked), 'fwd_T', 'adj_T', 'fwd_launches', 'adj_launches', 'fwd_overlap' /
+        'adj_overlap' (the hand-off overlap mode that runs, set_handoff_overlap)} of a
         call with batch B (launches: time-loop kernel launches per call)."""
-        out = (ctypes.c_int32 * 6)()
+        out = (ctypes.c_int32 * 8)()
         _hip.check(self.lib.rdq_fwi_launch_info(self.handle, int(B), out), "rdq_fwi_launch_info")
         return {"fwd_persistent": bool(out[0]), "adj_persistent": bool(out[1]),
                 "fwd_class": int(out[0]), "adj_class": int(out[1]), "fwd_T": int(out[2]),
-                "adj_T": int(out[3]), "fwd_launches": int(out[4]), "adj_launches": int(out[5])}
+                "adj_T": int(out[3]), "fwd_launches": int(out[4]), "adj_launches": int(out[5]),
+                "fwd_overlap": int(out[6]), "adj_overlap": int(out[7])}
 
     def set_sweep_delay(self, fwd_ticks, adj_ticks):
         """Persistent kernels: 10 ns ticks between an epoch's publish and its first hand-off pass."""
         _hip.check(self.lib.rdq_fwi_set_sweep_delay(self.handle, int(fwd_ticks), int(adj_ticks)),
                    "rdq_fwi_set_sweep_delay")
+
+    def set_handoff_overlap(self, fwd_mode, adj_mode):
+        """Persistent kernels: 0 = the hand-off sweep, then the post-sweep work; adjoint 1 (default) = the
+        dead cells zeroed while the sweep's first pass is in flight.  The forward has mode 0 only.  Results
+        are bit-identical in both modes."""
+        _hip.check(self.lib.rdq_fwi_set_handoff_overlap(self.handle, int(fwd_mode), int(adj_mode)),
+                   "rdq_fwi_set_handoff_overlap")
 
     def wide_info(self, B):
         """{'chains', 'fwd_spw', 'adj_spw', 'chain0_shots'}: the wide chunked kernels' concurrent launch
@@ -191,6 +200,15 @@ class FwiPlan:
             res[name] = {"wait_us": out[o] / n / 100.0, "steps_us": out[o + 1] / n / 100.0,
                          "publish_us": out[o + 2] / n / 100.0, "waves": int(out[o + 3]),
                          "first_pass_us": out[o + 4] / n / 100.0, "passes": out[o + 5] / n}
+        sp = (ctypes.c_uint64 * 10)()
+        _hip.check(self.lib.rdq_fwi_profile_split(self.handle, sp), "rdq_fwi_profile_split")
+        for name, o in (("fwd", 0), ("adj", 5)):
+            n = max(res[name]["waves"], 1)
+            # wait_us = a + b + c + d; publish_us = publish_issue_us + gradient_us
+            res[name].update({"wait_a_issue_us": sp[o] / n / 100.0, "wait_b_first_us": sp[o + 1] / n / 100.0,
+                              "wait_c_later_us": sp[o + 2] / n / 100.0, "wait_d_tail_us": sp[o + 3] / n / 100.0,
+                              "gradient_us": sp[o + 4] / n / 100.0,
+                              "publish_issue_us": res[name]["publish_us"] - sp[o + 4] / n / 100.0})
         return res
 
     def profile_waves(self, adj):
@@ -199,6 +217,16 @@ class FwiPlan:
         out = (ctypes.c_uint64 * n)()
         _hip.check(self.lib.rdq_fwi_profile_waves(self.handle, int(bool(adj)), out, n), "rdq_fwi_profile_waves")
         return np.frombuffer(out, dtype=np.uint64).reshape(-1, 3).astype(np.float64) / 100.0
+
+    def profile_waves_split(self, adj, ticks=False):
+        """(blocks*16, 8) per-wave {hand-off, steps, publish, a, b, c, d, gradient} us (ticks: the raw 10 ns
+        counts) of the last read_profile(): hand-off = a + b + c + d (rdq_fwi_profile_split)."""
+        n = 4096 * 16 * 8
+        out = (ctypes.c_uint64 * n)()
+        _hip.check(self.lib.rdq_fwi_profile_waves_split(self.handle, int(bool(adj)), out, n),
+                   "rdq_fwi_profile_waves_split")
+        raw = np.frombuffer(out, dtype=np.uint64).reshape(-1, 8)
+        return raw.copy() if ticks else raw.astype(np.float64) / 100.0
 
     def set_tuning(self, fwd_steps, adj_steps, chains=0):
         """Blocking depths (1..4) and concurrent launch chains of the chunked kernels (0 = auto)."""

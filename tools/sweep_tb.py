@@ -1,5 +1,11 @@
 """Time the forward / adjoint time loops for every temporal-blocking depth (steps per launch).
-python tools/sweep_tb.py [--ns 8] [--B 1]"""
+python tools/sweep_tb.py [--ns 8] [--B 1]
+--profile adds the persistent kernels' phase counters (per-wave averages, us): the hand-off wait and its
+split wait_a_issue / wait_b_first / wait_c_later / wait_d_tail, publish_issue and the adjoint's gradient.
+--overlap F,A sets the hand-off overlap modes; --ab N times the mode pairs of --ab-modes (default "0,0;0,1":
+the first is the baseline) alternated N times each, event-timed per kernel: one JSON line per run and a
+summary line with the bar a mode has to pass (every run faster than every baseline run, and the medians
+apart by at least three times the larger min-max spread)."""
 import argparse
 import json
 import os
@@ -24,6 +30,9 @@ ap.add_argument("--profile", action="store_true", help="phase counters of the pe
 ap.add_argument("--mode", type=int, default=1, help="persistent mode: 1 auto, 12 / 8 region height")
 ap.add_argument("--rw", default=None, help="rows per wave of the 96-row kernels, 'fwd,adj' (e.g. 12,12)")
 ap.add_argument("--delay", default=None, help="pre-sweep delays of the persistent kernels, 'fwd,adj' ticks")
+ap.add_argument("--overlap", default=None, help="hand-off overlap modes of the persistent kernels, 'fwd,adj'")
+ap.add_argument("--ab", type=int, default=0, help="rounds of an alternated A/B of hand-off overlap modes")
+ap.add_argument("--ab-modes", default="0,0;0,1", help="'fwd,adj' mode pairs of the A/B, baseline first")
 a = ap.parse_args()
 dev = torch.device("cuda:0")
 ctx = dict(n_grid=70, nt=a.nt, dx=10.0, dt=0.001, nbc=120, f=15.0, sz=10, gz=10, ng=70, ns=a.ns)
@@ -34,8 +43,63 @@ if a.rw:
     plan.set_rows_per_wave(*[int(x) for x in a.rw.split(",")])
 if a.delay:
     plan.set_sweep_delay(*[int(x) for x in a.delay.split(",")])
+if a.overlap:
+    plan.set_handoff_overlap(*[int(x) for x in a.overlap.split(",")])
 sz = plan.sizes(a.B)
 dseis = torch.randn(a.B, a.ns, sz.nrec, plan.ng, device=dev)
+
+
+def timed(reps):
+    """Medians (ms) of the forward's and the adjoint's event-timed durations over `reps` calls after one."""
+    ev = [torch.cuda.Event(enable_timing=True) for _ in range(3)]
+    fw, ad = [], []
+    for i in range(reps + 1):
+        coeffs, vstat = plan.coeffs(v, 0)
+        ev[0].record()
+        seis, hist = plan.forward(coeffs, a.B, keep_history=True)
+        ev[1].record()
+        plan.adjoint(coeffs, hist, dseis, a.B)
+        ev[2].record()
+        torch.cuda.synchronize()
+        if i:
+            fw.append(ev[0].elapsed_time(ev[1]))
+            ad.append(ev[1].elapsed_time(ev[2]))
+        del hist
+    plan.status()
+    return sorted(fw)[len(fw) // 2], sorted(ad)[len(ad) // 2]
+
+
+if a.ab:
+    plan.set_tuning(4, 4, 1)
+    plan.set_persistent(a.mode)
+    pairs = [tuple(int(x) for x in m.split(",")) for m in a.ab_modes.split(";")]
+    runs = {m: [] for m in pairs}
+    timed(a.reps)                                         # warm-up (clocks, allocator), not recorded
+    for rnd in range(a.ab):
+        for m in pairs:
+            plan.set_handoff_overlap(*m)
+            info = plan.launch_info(a.B)
+            assert (info["fwd_overlap"], info["adj_overlap"]) == m, info
+            fw, ad = timed(a.reps)
+            runs[m].append((fw, ad))
+            print(json.dumps({"round": rnd, "overlap": list(m), "fwd_ms": round(fw, 4), "adj_ms": round(ad, 4)}),
+                  flush=True)
+    summ = {}
+    for k, name in ((0, "fwd"), (1, "adj")):
+        base = sorted(r[k] for r in runs[pairs[0]])
+        for m in pairs[1:]:
+            if m[k] == pairs[0][k]:
+                continue
+            new = sorted(r[k] for r in runs[m])
+            spread = max(base[-1] - base[0], new[-1] - new[0])
+            gain = base[len(base) // 2] - new[len(new) // 2]
+            summ[f"{name} {pairs[0][k]}->{m[k]} (pair {m[0]},{m[1]})"] = {
+                "base_ms": [round(x, 4) for x in base], "new_ms": [round(x, 4) for x in new],
+                "median_gain_ms": round(gain, 4), "max_spread_ms": round(spread, 4),
+                "every_new_beats_every_base": new[-1] < base[0], "gain_over_3_spreads": gain >= 3 * spread}
+    print(json.dumps({"ab_summary": summ, "ns": a.ns, "nt": a.nt, "reps": a.reps}), flush=True)
+    sys.exit(0)
+
 res = []
 # (T, persistent)
 cfgs = [(a.only, a.mode)] if a.only else [(2, a.mode), (3, a.mode), (4, a.mode)]
@@ -61,6 +125,7 @@ for T, G in cfgs:
     plan.status()
     fw, ad = sorted(fw)[len(fw) // 2], sorted(ad)[len(ad) // 2]
     res.append({"T": T, "persistent": G, "mode": a.mode, "rw": a.rw, "delay": a.delay, "ns": a.ns,
+                "overlap": [plan.launch_info(a.B)["fwd_overlap"], plan.launch_info(a.B)["adj_overlap"]],
                 "fwd_launches": plan.launch_info(a.B)["fwd_launches"], "fwd_ms": round(fw, 3), "adj_ms": round(ad, 3),
                 "shot_ts_per_s": round(a.ns * a.nt * a.B / ((fw + ad) * 1e-3))})
     if a.profile and G:
