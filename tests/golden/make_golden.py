@@ -162,6 +162,45 @@ def gen_grad():
     save("grad_openfwi_ns1", v_true=v_true, v_init=v_init, y=y, loss=loss, grad=g, **ctx_arrays(ctx))
 
 
+def geometry_ctxs():
+    """Acquisition geometries beyond sz == gz with one receiver per column, on the SMALL grid."""
+    return {
+        # 40 receivers on 16 columns (default linspace): every column holds 2 or 3
+        "multi_rcv": dict(SMALL, ng=40),
+        # explicit gx with repeats out of order, two shots on one source column, source on the first
+        # model row and receivers on the last
+        "rcv_list": dict(SMALL, ng=7, sx=[3, 3, 12], gx=[5, 0, 5, 15, 5, 0, 9], sz=0, gz=150),
+        # source row and receiver row apart
+        "split_depth": dict(SMALL, sz=100, gz=10),
+    }
+
+
+def gen_geometry_paths():
+    """Forward seismograms (pde.py:82-83, the receiver gather) and the L1 gradient (its index backward
+    accumulates receivers that share a column) on the geometries of geometry_ctxs."""
+    ctxs = geometry_ctxs()
+    fw = make_fwi(ctxs["multi_rcv"])
+    c = fw.ctx
+    igx = fw.adj_sr(c["sx"], c["sz"], c["gx"], c["gz"], c["dx"], c["nbc"])[2]
+    counts = np.bincount(igx - c["nbc"], minlength=16)
+    assert counts.min() >= 2 and counts.max() >= 3, counts   # three terms: the fp32 order matters
+    v = synthetic.make_model("curvefault", 16, 16, seed=3, batch=2)
+    for tag, ctx in ctxs.items():
+        save("fwd_" + tag, v=v, seis=run_forward(ctx, v), **ctx_arrays(ctx))
+    v_true = synthetic.make_model("curvefault", 16, 16, seed=21, batch=2)
+    v_init = smooth(v_true, 2.0)
+    ctx = ctxs["multi_rcv"]
+    mask = np.ones((2, ctx["ns"], ctx["nt"], ctx["ng"]), np.float32)
+    mask[0, :, :, [2, 9, 10, 31]] = 0      # part of a column's receivers, and all of one's
+    mask[0, :, :, igx == igx[20]] = 0
+    mask[1, :, :, [0, 5, 39]] = 0
+    y, loss, g = l1_grad(ctx, v_true, v_init, mask=mask)
+    save("grad_multi_rcv", v_true=v_true, v_init=v_init, y=y, mask=mask, loss=loss, grad=g, **ctx_arrays(ctx))
+    ctx = ctxs["rcv_list"]
+    y, loss, g = l1_grad(ctx, v_true, v_init)
+    save("grad_rcv_list", v_true=v_true, v_init=v_init, y=y, loss=loss, grad=g, **ctx_arrays(ctx))
+
+
 class _NoDiffusion:
     device = torch.device("cpu")
 
@@ -664,6 +703,7 @@ def gen_post():
 
 
 GENS = dict(geometry=gen_geometry, damp=gen_damp, forward=gen_forward, grad=gen_grad,
+            geometry_paths=gen_geometry_paths,
             loop=gen_loop, unet=gen_unet, red=gen_red, small_losses=gen_small_losses, dfwi=gen_dfwi,
             ilvr=gen_ilvr, loop_rng=gen_loop_rng, loop_red=gen_loop_red, initial=gen_initial, ckpt=gen_ckpt,
             loop_red_configs2=gen_loop_red_configs2, post=gen_post, loop_red_b25=gen_loop_red_b25,

@@ -7,7 +7,9 @@ from conftest import ctx_of, load_golden, vnorm
 from oracle import oracle as O
 
 FWD = [("fwd_small", {}), ("fwd_small_st3", dict(sample_temporal=3, sample_spatial=0.5)), ("fwd_wrap", {}),
-       ("fwd_openfwi_ns1", {}), ("fwd_openfwi_ns5_nt400", {})]
+       ("fwd_openfwi_ns1", {}), ("fwd_openfwi_ns5_nt400", {}),
+       # several receivers per column, repeated gx / shared source column, source row != receiver row
+       ("fwd_multi_rcv", {}), ("fwd_rcv_list", {}), ("fwd_split_depth", {})]
 
 
 @pytest.mark.parametrize("name,kw", FWD)
@@ -19,7 +21,8 @@ def test_oracle_forward_bitexact(name, kw):
     assert np.array_equal(seis.view(np.int32), z["seis"].view(np.int32)), "oracle must be bit-exact"
 
 
-@pytest.mark.parametrize("name", ["grad_small", "grad_small_mask", "grad_openfwi_ns1"])
+@pytest.mark.parametrize("name", ["grad_small", "grad_small_mask", "grad_openfwi_ns1", "grad_multi_rcv",
+                                  "grad_rcv_list"])
 def test_oracle_gradient(name):
     z = load_golden(name)
     f = O.OracleFWI(ctx_of(z), z["v_init"].shape[0])
