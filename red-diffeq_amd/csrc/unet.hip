@@ -673,14 +673,6 @@ bool cc_ok(const rdq_conv_desc *d)
            xy * d->cout < lim;
 }
 
-void cc_extents(CcArgs &c, const rdq_conv_desc *d)
-{
-    const int64_t xy = (int64_t)d->B * d->H * d->W * 4;
-    c.xbytes = (int)(d->in_mode == RDQ_IN_UPSAMPLE2 ? xy / 4 * d->cin1 : xy * d->cin1);
-    c.x2bytes = (int)(xy * d->cin2);
-    c.wbytes = (int)((int64_t)d->cout * c.K * 4);
-}
-
 // splits: fill the chip with about one workgroup per CU, >= 3 stages per split (the pipeline's fill),
 // at most 16 slabs to combine; a grid of 128..255 tiles (half the CUs idle, or one workgroup
 // per CU with nothing to hide its waits) is split in two when each half keeps >= 6 stages (a
@@ -702,6 +694,36 @@ int cc_splits(const rdq_conv_desc *d, size_t ws_bytes, int *per_split)
     *per_split = per;
     return (nstages + per - 1) / per;
 }
+
+// when a channel-chunk conv may split K over the slabs it was given
+enum CcSplit {
+    CC_SPLIT_ANY,    // rdq_conv2d: always; without tickets the slabs are combined by k_conv_reduce
+    CC_SPLIT_FOLD,   // only with tickets: the kernel's epilogue (statistics, RMS, pair) needs the in-launch combine
+};
+
+// arguments of k_conv_cc / k_conv_cc_pair / k_conv_cc_lsm for a cc_ok descriptor, all but the tensors: extents,
+// K, stages and the K split within the slab_bytes at `part` (null: no split); the caller sets x .. y, gnp, rms_g
+CcArgs cc_args(const rdq_conv_desc *d, void *part, size_t slab_bytes, unsigned *tickets, CcSplit rule)
+{
+    CcArgs c{};
+    const int cin = d->cin1 + d->cin2;
+    c.d = *d;
+    c.part = static_cast<float *>(part);
+    c.tickets = tickets;
+    c.K = cin * d->kh * d->kw;
+    c.HW = d->H * d->W;
+    c.M = d->B * c.HW;
+    const int64_t xy = (int64_t)d->B * d->H * d->W * 4;
+    c.xbytes = (int)(d->in_mode == RDQ_IN_UPSAMPLE2 ? xy / 4 * d->cin1 : xy * d->cin1);
+    c.x2bytes = (int)(xy * d->cin2);
+    c.wbytes = (int)((int64_t)d->cout * c.K * 4);
+    c.nstages = cin / (d->kh == 3 ? CcCfg<9>::CPS : CcCfg<1>::CPS);
+    c.per_split = c.nstages;
+    c.S = part && (tickets || rule == CC_SPLIT_ANY) ? cc_splits(d, slab_bytes, &c.per_split) : 1;
+    return c;
+}
+
+dim3 cc_grid(const CcArgs &c) { return dim3((c.M + CC_BM - 1) / CC_BM, (c.d.cout + CC_BN - 1) / CC_BN, c.S); }
 
 // split count: about one workgroup per CU over the tile grid, >= 4 K stages per split, and the
 // partial slabs within the caller's workspace
@@ -3475,37 +3497,58 @@ static std::atomic<int> g_opt_gen{0};
 static int64_t conv3_tiles(const rdq_conv_desc *d)
 {
     if (d->kh != 3 || d->kw != 3 || d->pad != 1) return 0;
-    if (d->in_mode != RDQ_IN_PLAIN && d->in_mode != RDQ_IN_UPSAMPLE2) return false;
-    if (d->cin1 % 8 || d->cin2 % 8 || d->cout % C3_BN || d->W > C3_WMAX || d->B >= 4096) return false;
+    if (d->in_mode != RDQ_IN_PLAIN && d->in_mode != RDQ_IN_UPSAMPLE2) return 0;
+    if (d->cin1 % 8 || d->cin2 % 8 || d->cout % C3_BN || d->W > C3_WMAX || d->B >= 4096) return 0;
     const int64_t HW = (int64_t)d->H * d->W, M = d->B * HW;
-    if (HW >= (1 << 20) || M >= (int64_t)1 << 30) return false;
+    if (HW >= (1 << 20) || M >= (int64_t)1 << 30) return 0;
     // the halo gather addresses each input tensor with 31-bit byte offsets (buffer loads)
     const int64_t plane = d->in_mode == RDQ_IN_UPSAMPLE2 ? HW / 4 : HW;
-    if ((int64_t)d->B * std::max(d->cin1, d->cin2) * plane * 4 >= (int64_t)1 << 31) return false;
-    if (M * d->cout * 4 >= (int64_t)1 << 31) return false;     // output / residual: the same, epilogue
+    if ((int64_t)d->B * std::max(d->cin1, d->cin2) * plane * 4 >= (int64_t)1 << 31) return 0;
+    if (M * d->cout * 4 >= (int64_t)1 << 31) return 0;         // output / residual: the same, epilogue
     return (M + C3_BM - 1) / C3_BM * (d->cout / C3_BN);
 }
 bool conv3_ok(const rdq_conv_desc *d) { return conv3_tiles(d) >= C3_MIN_TILES; }
 bool conv3f_ok(const rdq_conv_desc *d) { return C3F_MIN_TILES > 0 && conv3_tiles(d) >= C3F_MIN_TILES; }
 
-// k_conv3_f32 on a conv3f_ok descriptor (raw fp32 weights); gnp: GroupNorm partials (bm = C3_BM) or null
-void launch_conv3_f32(const rdq_conv_desc *d, const float *x, const float *x2, const float *w, const float *bias,
-                      const float *res, float *y, double *gnp, int G, hipStream_t st)
+// arguments of the halo-staged 3x3 kernels for a conv3_tiles descriptor, all but the tensors; BK: the kernel's
+// channel chunk (k_conv3_f32: C3F_BK, k_conv3_bf16: BF_BK)
+C3Args c3_args(const rdq_conv_desc *d, int BK)
 {
     C3Args c{};
-    c.d = *d; c.x = x; c.x2 = x2; c.wf = w; c.bias = bias; c.res = res; c.y = y; c.gnp = gnp; c.G = G;
-    c.cinp = (d->cin1 + d->cin2 + C3F_BK - 1) / C3F_BK * C3F_BK;
+    c.d = *d;
+    c.cinp = (d->cin1 + d->cin2 + BK - 1) / BK * BK;
     c.K = 9 * c.cinp;
     c.HW = d->H * d->W;
     c.M = d->B * c.HW;
     c.R = C3_BM + 2 * d->W + 2;
-    c.cch = c.cinp / C3F_BK;
+    c.cch = c.cinp / BK;
     c.plane = d->in_mode == RDQ_IN_UPSAMPLE2 ? c.HW / 4 : c.HW;
-    const dim3 grid((c.M + C3_BM - 1) / C3_BM, d->cout / C3_BN);
+    return c;
+}
+
+dim3 c3_grid(const C3Args &c) { return dim3((c.M + C3_BM - 1) / C3_BM, c.d.cout / C3_BN); }
+
+// k_conv3_f32 on a conv3f_ok descriptor (raw fp32 weights); gnp: GroupNorm partials (bm = C3_BM) or null
+void launch_conv3_f32(const rdq_conv_desc *d, const float *x, const float *x2, const float *w, const float *bias,
+                      const float *res, float *y, double *gnp, int G, hipStream_t st)
+{
+    C3Args c = c3_args(d, C3F_BK);
+    c.x = x; c.x2 = x2; c.wf = w; c.bias = bias; c.res = res; c.y = y; c.gnp = gnp; c.G = G;
     if (d->in_mode == RDQ_IN_UPSAMPLE2)
-        hipLaunchKernelGGL(HIP_KERNEL_NAME(k_conv3_f32<RDQ_IN_UPSAMPLE2>), grid, dim3(256), 0, st, c);
+        hipLaunchKernelGGL(HIP_KERNEL_NAME(k_conv3_f32<RDQ_IN_UPSAMPLE2>), c3_grid(c), dim3(256), 0, st, c);
     else
-        hipLaunchKernelGGL(HIP_KERNEL_NAME(k_conv3_f32<RDQ_IN_PLAIN>), grid, dim3(256), 0, st, c);
+        hipLaunchKernelGGL(HIP_KERNEL_NAME(k_conv3_f32<RDQ_IN_PLAIN>), c3_grid(c), dim3(256), 0, st, c);
+}
+
+// k_conv3_bf16 on a conv3_ok descriptor; in8: the input is c.x8 (bf16 octets, plain mode)
+void launch_conv3_bf16(const C3Args &c, bool in8, hipStream_t st)
+{
+    if (in8)
+        hipLaunchKernelGGL(HIP_KERNEL_NAME(k_conv3_bf16<RDQ_IN_PLAIN, true>), c3_grid(c), dim3(256), 0, st, c);
+    else if (c.d.in_mode == RDQ_IN_UPSAMPLE2)
+        hipLaunchKernelGGL(HIP_KERNEL_NAME(k_conv3_bf16<RDQ_IN_UPSAMPLE2>), c3_grid(c), dim3(256), 0, st, c);
+    else
+        hipLaunchKernelGGL(HIP_KERNEL_NAME(k_conv3_bf16<RDQ_IN_PLAIN>), c3_grid(c), dim3(256), 0, st, c);
 }
 
 int bf_cinp(const rdq_conv_desc *d) { return (d->cin1 + d->cin2 + BF_BK - 1) / BF_BK * BF_BK; }
@@ -3557,27 +3600,44 @@ bool conv_desc_ok(const rdq_conv_desc *d)
     if (d->in_mode == RDQ_IN_UPSAMPLE2 && ((d->H | d->W) & 1 || d->cin2 != 0)) return false;
     return true;
 }
-}  // namespace
 
-// the small-image form is its own instantiation (the per-channel form's code is unchanged by it)
-// (gn4: gn_grid chose 4096-element chunks: the k_gn_apply_t<false, 4> instantiation)
-#define LAUNCH_GN_T(GRID, ST, ...)                                                                     \
-    do {                                                                                               \
-        if (nch < 0) hipLaunchKernelGGL(HIP_KERNEL_NAME(k_gn_apply_t<true>), GRID, dim3(256), 0, ST, __VA_ARGS__); \
-        else if (gn4) hipLaunchKernelGGL(HIP_KERNEL_NAME(k_gn_apply_t<false, 4>), GRID, dim3(256), 0, ST, __VA_ARGS__); \
-        else hipLaunchKernelGGL(HIP_KERNEL_NAME(k_gn_apply_t<false>), GRID, dim3(256), 0, ST, __VA_ARGS__);      \
-    } while (0)
-#define LAUNCH_GN_TB(GRID, ST, ...)                                                                    \
-    do {                                                                                               \
-        if (nch < 0) hipLaunchKernelGGL(HIP_KERNEL_NAME(k_gn_apply_t<true, 1, __bf16>), GRID, dim3(256), 0, ST, __VA_ARGS__); \
-        else if (gn4) hipLaunchKernelGGL(HIP_KERNEL_NAME(k_gn_apply_t<false, 4, __bf16>), GRID, dim3(256), 0, ST, __VA_ARGS__); \
-        else hipLaunchKernelGGL(HIP_KERNEL_NAME(k_gn_apply_t<false, 1, __bf16>), GRID, dim3(256), 0, ST, __VA_ARGS__); \
-    } while (0)
-#define LAUNCH_GN(GRID, ST, ...)                                                                       \
-    do {                                                                                               \
-        if (nch < 0) hipLaunchKernelGGL(HIP_KERNEL_NAME(k_gn_apply<true>), GRID, dim3(256), 0, ST, __VA_ARGS__);   \
-        else hipLaunchKernelGGL(HIP_KERNEL_NAME(k_gn_apply<false>), GRID, dim3(256), 0, ST, __VA_ARGS__);        \
-    } while (0)
+// the input check of every conv entry point: a sound descriptor, x, and x2 where a concat reads it (the mode
+// term keeps what rdq_conv2d always accepted; with a mode, conv_desc_ok has already required cin2 == 0)
+bool conv_in_ok(const rdq_conv_desc *d, const void *x, const void *x2)
+{
+    return conv_desc_ok(d) && x && !(d->cin2 > 0 && !x2 && d->in_mode == RDQ_IN_PLAIN);
+}
+
+// k_conv_reduce over S slabs at part: the split-K combine as its own launch
+void launch_conv_reduce(int S, const rdq_conv_desc *d, const float *part, const float *bias, const float *res, float *y,
+                        hipStream_t st)
+{
+    const int HW = d->H * d->W;
+    const int64_t total = (int64_t)d->B * HW * d->cout;
+    hipLaunchKernelGGL(k_conv_reduce, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, st, S, total, d->cout, HW, part,
+                       bias, res, y);
+}
+
+// the n linears of rdq_linear_silu_multi as kernel arguments; false: a null weight / output or an empty linear
+bool lin_multi(LinMulti &L, int n, const float *const *w, const float *const *b, const int32_t *out, float *const *y)
+{
+    L = LinMulti{};
+    L.n = n;
+    L.start[0] = 0;
+    for (int j = 0; j < n; ++j) {
+        if (!w[j] || !y[j] || out[j] < 1) return false;
+        L.w[j] = w[j];
+        L.b[j] = b ? b[j] : nullptr;
+        L.y[j] = y[j];
+        L.out[j] = out[j];
+        L.start[j + 1] = L.start[j] + out[j];
+    }
+    return true;
+}
+
+// SinusoidalPosEmb's frequency step ln(theta) / (half - 1), rounded as python's float math rounds it
+float sinusoidal_step(int dim, float theta) { return (float)(std::log((double)theta) / (double)(dim / 2 - 1)); }
+}  // namespace
 
 // GroupNorm pass grid: one workgroup per (channel, 1024-element chunk) of a group, or for images of
 // <= 512 pixels in grids of more than 8192 workgroups -nch = 1024 / HW whole channels per workgroup
@@ -3597,6 +3657,95 @@ static int gn_grid(int B, int C, int G, int HW, int *nch, bool *gn4 = nullptr)
     if (gn4) *gn4 = chunk == 4096;
     *nch = (HW + chunk - 1) / chunk;
     return cpg * *nch;
+}
+
+// the normalise pass of a fused conv + GroupNorm Block on the conv's output h (TX: fp32, or the bf16 the halo-
+// staged conv holds it as) and the partial statistics gnp its epilogue left per bm-pixel tile: gn_grid's grid
+// and the k_gn_apply_t instantiation that goes with it (the small-image form and the 4096-element chunks are
+// instantiations of their own, so the per-channel form's code is unchanged by them)
+template <typename TX>
+static void launch_gn_apply_t(const rdq_conv_desc *d, int G, const TX *h, const float *gamma, const float *beta,
+                              const float *ss, const double *gnp, float eps, const float *post, float *y, int bm,
+                              hipStream_t st)
+{
+    const int C = d->cout, HW = d->H * d->W;
+    int nch = 0;
+    bool gn4 = false;
+    const dim3 grid(gn_grid(d->B, C, G, HW, &nch, &gn4), d->B * G);
+    if (nch < 0)
+        hipLaunchKernelGGL(HIP_KERNEL_NAME(k_gn_apply_t<true, 1, TX>), grid, dim3(256), 0, st, C, HW, G, nch, h, gamma,
+                           beta, ss, gnp, eps, post, y, bm);
+    else if (gn4)
+        hipLaunchKernelGGL(HIP_KERNEL_NAME(k_gn_apply_t<false, 4, TX>), grid, dim3(256), 0, st, C, HW, G, nch, h, gamma,
+                           beta, ss, gnp, eps, post, y, bm);
+    else
+        hipLaunchKernelGGL(HIP_KERNEL_NAME(k_gn_apply_t<false, 1, TX>), grid, dim3(256), 0, st, C, HW, G, nch, h, gamma,
+                           beta, ss, gnp, eps, post, y, bm);
+}
+
+// the same pass with the U-Net's final 1x1 conv (nf <= GO_MAXF channels) applied to its result: k_gn_apply_out
+template <typename TX>
+static void launch_gn_apply_out(const rdq_conv_desc *d, int G, const TX *h, const float *gamma, const float *beta,
+                                const float *ss, const double *gnp, float eps, const float *post, int nf,
+                                const float *wf, const float *bf, float *yf, int bm, hipStream_t st)
+{
+    const int HW = d->H * d->W;
+    hipLaunchKernelGGL(HIP_KERNEL_NAME(k_gn_apply_out<TX>), dim3((HW + 63) / 64, d->B), dim3(64 * GO_NW), 0, st, d->cout,
+                       HW, G, h, gamma, beta, ss, gnp, eps, post, nf, wf, bf, yf, bm);
+}
+
+// the fused LinearAttention's pixel chunks of nsub 64-pixel tiles (at least `least`, at most 16): about
+// `target` workgroups per launch
+static void lab_split(int B, int n, int target, int least, int *nsub, int *nch)
+{
+    const int tiles = (n + LB_PX - 1) / LB_PX;
+    int s = (int)std::min<int64_t>(16, std::max<int64_t>(least, ((int64_t)tiles * B + target - 1) / target));
+    s = std::min(s, tiles);
+    *nsub = s;
+    *nch = (tiles + s - 1) / s;
+}
+
+// bf16 form: 2048 workgroups, chunks of >= 2 tiles; fp32 form (F): 1024 and 1 (small batches: the combine
+// reads every chunk's partials)
+template <bool F>
+static void lab_split(int B, int n, int *nsub, int *nch) { lab_split(B, n, F ? 1024 : 2048, F ? 1 : 2, nsub, nch); }
+
+template <bool F>
+static size_t lab_ws_bytes(int B, int dim, int n)
+{
+    if (B < 1 || n < 1 || (dim != 64 && dim != 128)) return 0;
+    int nsub, nch;
+    lab_split<F>(B, n, &nsub, &nch);
+    return (size_t)B * nch * LB_PART * sizeof(float);
+}
+
+// rdq_linear_attention_bf16 (wqkv / wout: packed bf16) and, F, rdq_linear_attention_f32 (the module's fp32 weights)
+template <bool F>
+static int linear_attention_fused(int B, int dim, int n, int nmem, float scale, const float *x, const float *g_in,
+                                  const void *wqkv, const float *mem_kv, const void *wout, const float *b_out,
+                                  const float *g_out, float *y, void *ws, size_t ws_bytes, hipStream_t st)
+{
+    if (B < 1 || n < 1 || nmem < 0 || (dim != 64 && dim != 128) || !x || !g_in || !wqkv ||
+        (nmem > 0 && !mem_kv) || !wout || !g_out || !y || !ws || y == x)
+        return RDQ_E_INVALID;
+    if ((int64_t)B * dim * n >= ((int64_t)1 << 31) || ws_bytes < lab_ws_bytes<F>(B, dim, n)) return RDQ_E_INVALID;
+    LabArgs a{};
+    a.x = x; a.g_in = g_in; a.mem = mem_kv; a.b_out = b_out; a.g_out = g_out;
+    if (F) { a.wqkv32 = static_cast<const float *>(wqkv); a.wout32 = static_cast<const float *>(wout); }
+    else { a.wqkv = static_cast<const __bf16 *>(wqkv); a.wout = static_cast<const __bf16 *>(wout); }
+    a.part = static_cast<float *>(ws); a.y = y;
+    a.n = n; a.nmem = nmem; a.scale = scale;
+    lab_split<F>(B, n, &a.nsub, &a.nch);
+    const dim3 grid(a.nch, B);
+    if (dim == 64) {
+        hipLaunchKernelGGL(HIP_KERNEL_NAME(k_lab_kv<64, F>), grid, dim3(256), 0, st, a);
+        hipLaunchKernelGGL(HIP_KERNEL_NAME(k_lab_out<64, F>), grid, dim3(256), 0, st, a);
+    } else {
+        hipLaunchKernelGGL(HIP_KERNEL_NAME(k_lab_kv<128, F>), grid, dim3(256), 0, st, a);
+        hipLaunchKernelGGL(HIP_KERNEL_NAME(k_lab_out<128, F>), grid, dim3(256), 0, st, a);
+    }
+    RDQ_CHECK(hipGetLastError());
+    return 0;
 }
 
 extern "C" {
@@ -3624,39 +3773,20 @@ size_t rdq_conv2d_ws_bytes(const rdq_conv_desc *d)
 int rdq_conv2d(const rdq_conv_desc *d, const float *x, const float *x2, const float *w, const float *bias,
                const float *residual, float *y, void *ws, size_t ws_bytes, uint32_t *tickets, hipStream_t st)
 {
-    if (!d || !x || !w || !y || d->B < 1 || d->cin1 < 1 || d->cout < 1 || d->kh < 1 || d->kw < 1 || d->H < 1 ||
-        d->W < 1 || d->pad < 0 || (d->cin2 > 0 && !x2 && d->in_mode == RDQ_IN_PLAIN))
-        return RDQ_E_INVALID;
-    if (d->in_mode == RDQ_IN_UNSHUFFLE2 && (d->cin1 % 4 != 0 || d->cin2 != 0)) return RDQ_E_INVALID;
-    if (d->in_mode == RDQ_IN_UPSAMPLE2 && ((d->H | d->W) & 1 || d->cin2 != 0)) return RDQ_E_INVALID;
+    if (!conv_in_ok(d, x, x2) || !w || !y) return RDQ_E_INVALID;
     if (conv3f_ok(d)) {
         launch_conv3_f32(d, x, x2, w, bias, residual, y, nullptr, 0, st);
         RDQ_CHECK(hipGetLastError());
         return 0;
     }
     if (cc_ok(d)) {
-        CcArgs c{};
-        c.d = *d; c.x = x; c.x2 = x2; c.w = w; c.bias = bias; c.res = residual; c.y = y;
-        c.part = static_cast<float *>(ws);
-        c.tickets = tickets;
-        c.K = (d->cin1 + d->cin2) * d->kh * d->kw;
-        c.HW = d->H * d->W;
-        c.M = d->B * c.HW;
-        cc_extents(c, d);
-        c.nstages = (d->cin1 + d->cin2) / (d->kh == 3 ? CcCfg<9>::CPS : CcCfg<1>::CPS);
-        c.S = ws ? cc_splits(d, ws_bytes, &c.per_split) : 1;
-        if (c.S == 1) c.per_split = c.nstages;
-        const bool fold = c.S > 1 && tickets;        // combine in the conv launch
-        if (c.S > 1 && !tickets) c.tickets = nullptr;
-        const dim3 grid((c.M + CC_BM - 1) / CC_BM, (d->cout + CC_BN - 1) / CC_BN, c.S);
-        CcArgs cl = c;
-        if (c.S > 1 && !fold) cl.S = -c.S;            // slabs only; k_conv_reduce combines
-        launch_cc(cl, grid, st);
-        if (c.S > 1 && !fold) {
-            const int64_t total = (int64_t)c.M * d->cout;
-            hipLaunchKernelGGL(k_conv_reduce, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, st, c.S, total,
-                               d->cout, c.HW, c.part, bias, residual, y);
-        }
+        CcArgs c = cc_args(d, ws, ws_bytes, tickets, CC_SPLIT_ANY);
+        c.x = x; c.x2 = x2; c.w = w; c.bias = bias; c.res = residual; c.y = y;
+        const dim3 grid = cc_grid(c);
+        const int S = c.S;
+        if (S > 1 && !tickets) c.S = -S;              // slabs only; k_conv_reduce combines
+        launch_cc(c, grid, st);
+        if (S > 1 && !tickets) launch_conv_reduce(S, d, c.part, bias, residual, y, st);
         RDQ_CHECK(hipGetLastError());
         return 0;
     }
@@ -3675,11 +3805,7 @@ int rdq_conv2d(const rdq_conv_desc *d, const float *x, const float *x2, const fl
     else if (sq && d->kh == 1) launch_conv_ig<1>(grid, st, a);
     else if (sq && d->kh == 7) launch_conv_ig<7>(grid, st, a);
     else launch_conv_ig<0>(grid, st, a);
-    if (a.S > 1) {
-        const int64_t total = (int64_t)a.M * d->cout;
-        hipLaunchKernelGGL(k_conv_reduce, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, st, a.S, total, d->cout,
-                           a.HW, a.part, bias, residual, y);
-    }
+    if (a.S > 1) launch_conv_reduce(a.S, d, a.part, bias, residual, y, st);
     RDQ_CHECK(hipGetLastError());
     return 0;
 }
@@ -3698,26 +3824,14 @@ static bool gn_conv_args(CcArgs &c, const rdq_conv_desc *d, const float *x, cons
                          const float *bias, int32_t G, void *ws, size_t ws_bytes, uint32_t *tickets)
 {
     const size_t need = rdq_conv2d_gn_ws_bytes(d, G);
-    if (!need || !x || !w || !ws || ws_bytes < need || (d->cin2 > 0 && !x2 && d->in_mode == RDQ_IN_PLAIN))
-        return false;
-    if (d->in_mode == RDQ_IN_UNSHUFFLE2 && (d->cin1 % 4 != 0 || d->cin2 != 0)) return false;
-    if (d->in_mode == RDQ_IN_UPSAMPLE2 && ((d->H | d->W) & 1 || d->cin2 != 0)) return false;
+    if (!need || !conv_in_ok(d, x, x2) || !w || !ws || ws_bytes < need) return false;
     const size_t M = (size_t)d->B * d->H * d->W;
     const size_t slabs = rdq_conv2d_ws_bytes(d);
     float *h = reinterpret_cast<float *>(static_cast<char *>(ws) + slabs);
-    c = CcArgs{};
-    c.d = *d; c.x = x; c.x2 = x2; c.w = w; c.bias = bias; c.res = nullptr; c.y = h;
-    c.part = static_cast<float *>(ws);
-    c.tickets = tickets;
+    c = cc_args(d, ws, slabs, tickets, CC_SPLIT_FOLD);       // statistics need the in-launch combine
+    c.x = x; c.x2 = x2; c.w = w; c.bias = bias; c.y = h;
     c.gnp = reinterpret_cast<double *>(h + M * d->cout);
     c.G = G;
-    c.K = (d->cin1 + d->cin2) * d->kh * d->kw;
-    c.HW = d->H * d->W;
-    c.M = (int)M;
-    cc_extents(c, d);
-    c.nstages = (d->cin1 + d->cin2) / (d->kh == 3 ? CcCfg<9>::CPS : CcCfg<1>::CPS);
-    c.S = (slabs && tickets) ? cc_splits(d, slabs, &c.per_split) : 1;   // statistics need the in-launch combine
-    if (c.S == 1) c.per_split = c.nstages;
     return true;
 }
 
@@ -3737,17 +3851,9 @@ int rdq_conv2d_gn_silu(const rdq_conv_desc *d, const float *x, const float *x2, 
 {
     CcArgs c;
     if (!y || !gamma || !beta || !gn_conv_args(c, d, x, x2, w, bias, G, ws, ws_bytes, tickets)) return RDQ_E_INVALID;
-    float *h = c.y;
-    double *gnp = c.gnp;
-    const dim3 grid((c.M + CC_BM - 1) / CC_BM, (d->cout + CC_BN - 1) / CC_BN, c.S);
     const int bm = conv3f_gn(c, d, G, st) ? C3_BM : CC_BM;    // launched there, or here:
-    if (bm == CC_BM) launch_cc(c, grid, st);
-    const int C = d->cout, HW = c.HW;
-    int nch = 0;
-    bool gn4 = false;
-    const int gxa = gn_grid(d->B, C, G, HW, &nch, &gn4);
-    LAUNCH_GN_T(dim3(gxa, d->B * G), st, C, HW, G, nch, h, gamma, beta,
-                       scale_shift, gnp, eps, post_residual, y, bm);
+    if (bm == CC_BM) launch_cc(c, cc_grid(c), st);
+    launch_gn_apply_t(d, G, c.y, gamma, beta, scale_shift, c.gnp, eps, post_residual, y, bm, st);
     RDQ_CHECK(hipGetLastError());
     return 0;
 }
@@ -3779,55 +3885,27 @@ int rdq_conv2d_gn_silu_sc(const rdq_conv_desc *d, const float *x, const float *x
                           float *y, int32_t cout_s, const float *w_s, const float *b_s, float *y_s, void *ws,
                           size_t ws_bytes, uint32_t *tickets, hipStream_t st)
 {
+    // block1's conv: exactly the arguments (and the input check) of rdq_conv2d_gn_silu; this form's own
+    // workspace is larger, and its size is 0 unless the input mode is plain, so x2 is checked as it was here
     const size_t need = rdq_conv2d_gn_sc_ws_bytes(d, G, cout_s);
-    if (!need || !x || !w || !y || !gamma || !beta || !w_s || !y_s || !ws || ws_bytes < need ||
-        (d->cin2 > 0 && !x2))
+    CcArgs c;
+    if (!need || !y || !gamma || !beta || !w_s || !y_s || ws_bytes < need ||
+        !gn_conv_args(c, d, x, x2, w, bias, G, ws, ws_bytes, tickets))
         return RDQ_E_INVALID;
+    // the shortcut: the arguments of rdq_conv2d, its slabs behind block1's area (split-K combined in the launch)
     const rdq_conv_desc ds = shortcut_desc(d, cout_s);
-    const size_t M = (size_t)d->B * d->H * d->W;
-    const size_t wa = rdq_conv2d_gn_ws_bytes(d, G), slabs = rdq_conv2d_ws_bytes(d), slabs_s = rdq_conv2d_ws_bytes(&ds);
-    float *h = reinterpret_cast<float *>(static_cast<char *>(ws) + slabs);
-    // block1's conv: exactly the arguments of rdq_conv2d_gn_silu
-    CcArgs c{};
-    c.d = *d; c.x = x; c.x2 = x2; c.w = w; c.bias = bias; c.res = nullptr; c.y = h;
-    c.part = static_cast<float *>(ws);
-    c.tickets = tickets;
-    c.gnp = reinterpret_cast<double *>(h + M * d->cout);
-    c.G = G;
-    c.K = (d->cin1 + d->cin2) * 9;
-    c.HW = d->H * d->W;
-    c.M = (int)M;
-    cc_extents(c, d);
-    c.nstages = (d->cin1 + d->cin2) / CcCfg<9>::CPS;
-    c.S = (slabs && tickets) ? cc_splits(d, slabs, &c.per_split) : 1;
-    if (c.S == 1) c.per_split = c.nstages;
-    // the shortcut: exactly the arguments of rdq_conv2d (split-K combined in the launch)
-    CcArgs e{};
-    e.d = ds; e.x = x; e.x2 = x2; e.w = w_s; e.bias = b_s; e.res = nullptr; e.y = y_s;
-    e.part = reinterpret_cast<float *>(static_cast<char *>(ws) + wa);
-    e.tickets = tickets ? tickets + rdq_conv2d_tickets(d) : nullptr;
-    e.K = ds.cin1 + ds.cin2;
-    e.HW = c.HW;
-    e.M = c.M;
-    cc_extents(e, &ds);
-    e.nstages = (ds.cin1 + ds.cin2) / CcCfg<1>::CPS;
-    e.S = (slabs_s && tickets) ? cc_splits(&ds, slabs_s, &e.per_split) : 1;
-    if (e.S == 1) e.per_split = e.nstages;
-    const int gy_a = (d->cout + CC_BN - 1) / CC_BN, gy_b = (cout_s + CC_BN - 1) / CC_BN;
+    CcArgs e = cc_args(&ds, static_cast<char *>(ws) + rdq_conv2d_gn_ws_bytes(d, G), rdq_conv2d_ws_bytes(&ds),
+                       tickets ? tickets + rdq_conv2d_tickets(d) : nullptr, CC_SPLIT_FOLD);
+    e.x = x; e.x2 = x2; e.w = w_s; e.bias = b_s; e.y = y_s;
     int bm = CC_BM;
     if (conv3f_gn(c, d, G, st)) {     // the 3x3 on the halo-staged kernel, the shortcut on its own
         bm = C3_BM;
-        launch_cc(e, dim3((e.M + CC_BM - 1) / CC_BM, gy_b, e.S), st);
+        launch_cc(e, cc_grid(e), st);
     } else {
-        const dim3 grid((c.M + CC_BM - 1) / CC_BM, gy_a + gy_b, std::max(c.S, e.S));
-        hipLaunchKernelGGL(k_conv_cc_pair, grid, dim3(256), 0, st, c, e, gy_a);
+        const dim3 gc = cc_grid(c), ge = cc_grid(e);
+        hipLaunchKernelGGL(k_conv_cc_pair, dim3(gc.x, gc.y + ge.y, std::max(c.S, e.S)), dim3(256), 0, st, c, e, (int)gc.y);
     }
-    const int C = d->cout, HW = c.HW;
-    int nch = 0;
-    bool gn4 = false;
-    const int gxa = gn_grid(d->B, C, G, HW, &nch, &gn4);
-    LAUNCH_GN_T(dim3(gxa, d->B * G), st, C, HW, G, nch, h, gamma, beta,
-                       scale_shift, c.gnp, eps, nullptr, y, bm);
+    launch_gn_apply_t(d, G, c.y, gamma, beta, scale_shift, c.gnp, eps, nullptr, y, bm, st);
     RDQ_CHECK(hipGetLastError());
     return 0;
 }
@@ -3839,35 +3917,23 @@ int rdq_conv2d_gn_silu_lsm(const rdq_conv_desc *d, const float *x, const float *
                            float *const *ly, int32_t ss_index, hipStream_t st)
 {
     CcArgs c;
-    if (!y || !gamma || !beta || !temb || in < 1 || n < 1 || n > LM_MAX || !lw || !lout || !ly ||
-        ss_index >= n || d->in_mode != RDQ_IN_PLAIN || !gn_conv_args(c, d, x, x2, w, bias, G, ws, ws_bytes, tickets))
+    LinMulti L;
+    if (!y || !gamma || !beta || !temb || in < 1 || n < 1 || n > LM_MAX || !lw || !lout || !ly || ss_index >= n ||
+        !gn_conv_args(c, d, x, x2, w, bias, G, ws, ws_bytes, tickets) || d->in_mode != RDQ_IN_PLAIN ||
+        !lin_multi(L, n, lw, lb, lout, ly))
         return RDQ_E_INVALID;
-    LinMulti L{};
-    L.n = n;
-    L.start[0] = 0;
-    for (int j = 0; j < n; ++j) {
-        if (!lw[j] || !ly[j] || lout[j] < 1) return RDQ_E_INVALID;
-        L.w[j] = lw[j];
-        L.b[j] = lb ? lb[j] : nullptr;
-        L.y[j] = ly[j];
-        L.out[j] = lout[j];
-        L.start[j + 1] = L.start[j] + lout[j];
-    }
     if (ss_index >= 0 && lout[ss_index] != 2 * d->cout) return RDQ_E_INVALID;
     const int per_b = (L.start[n] + 4 * LSM_RPW - 1) / (4 * LSM_RPW), nlsm = per_b * d->B;
-    const dim3 grid(nlsm + (c.M + CC_BM - 1) / CC_BM, (d->cout + CC_BN - 1) / CC_BN, c.S);
+    dim3 grid = cc_grid(c);
+    grid.x += nlsm;
     if (d->kh == 3)
         hipLaunchKernelGGL(HIP_KERNEL_NAME(k_conv_cc_lsm<9, RDQ_IN_PLAIN>), grid, dim3(256), 0, st, c, L, in, temb,
                            nlsm, per_b);
     else
         hipLaunchKernelGGL(HIP_KERNEL_NAME(k_conv_cc_lsm<1, RDQ_IN_PLAIN>), grid, dim3(256), 0, st, c, L, in, temb,
                            nlsm, per_b);
-    const int C = d->cout, HW = c.HW;
-    int nch = 0;
-    bool gn4 = false;
-    const int gxa = gn_grid(d->B, C, G, HW, &nch, &gn4);
-    LAUNCH_GN_T(dim3(gxa, d->B * G), st, C, HW, G, nch, c.y, gamma, beta,
-                       ss_index >= 0 ? ly[ss_index] : nullptr, c.gnp, eps, post_residual, y);
+    launch_gn_apply_t(d, G, c.y, gamma, beta, ss_index >= 0 ? ly[ss_index] : nullptr, c.gnp, eps, post_residual, y,
+                      CC_BM, st);
     RDQ_CHECK(hipGetLastError());
     return 0;
 }
@@ -3878,15 +3944,12 @@ int rdq_conv2d_gn_silu_out(const rdq_conv_desc *d, const float *x, const float *
                            void *ws, size_t ws_bytes, uint32_t *tickets, hipStream_t st)
 {
     CcArgs c;
-    if (!yf || !wf || !gamma || !beta || nf < 1 || nf > GO_MAXF || d->cout % 4 || G > 64 ||
-        !gn_conv_args(c, d, x, x2, w, bias, G, ws, ws_bytes, tickets))
+    if (!yf || !wf || !gamma || !beta || nf < 1 || nf > GO_MAXF || G > 64 ||
+        !gn_conv_args(c, d, x, x2, w, bias, G, ws, ws_bytes, tickets) || d->cout % 4)
         return RDQ_E_INVALID;
-    const dim3 grid((c.M + CC_BM - 1) / CC_BM, (d->cout + CC_BN - 1) / CC_BN, c.S);
     const int bm = conv3f_gn(c, d, G, st) ? C3_BM : CC_BM;    // launched there, or here:
-    if (bm == CC_BM) launch_cc(c, grid, st);
-    const int HW = c.HW;
-    hipLaunchKernelGGL(HIP_KERNEL_NAME(k_gn_apply_out<float>), dim3((HW + 63) / 64, d->B), dim3(64 * GO_NW), 0, st, d->cout, HW, G, c.y, gamma, beta,
-                       scale_shift, c.gnp, eps, post_residual, nf, wf, bf, yf, bm);
+    if (bm == CC_BM) launch_cc(c, cc_grid(c), st);
+    launch_gn_apply_out(d, G, c.y, gamma, beta, scale_shift, c.gnp, eps, post_residual, nf, wf, bf, yf, bm, st);
     RDQ_CHECK(hipGetLastError());
     return 0;
 }
@@ -3895,9 +3958,8 @@ int rdq_unet_head(const rdq_conv_desc *d, const float *x, const float *w, const 
                   float theta, const int64_t *t, const float *w1, const float *b1, int32_t hid, const float *w2,
                   const float *b2, int32_t out, float *temb, hipStream_t st)
 {
-    if (!d || !x || !w || !y || !t || !w1 || !b1 || !w2 || !b2 || !temb || d->B < 1 || d->cin1 < 1 ||
-        d->cin2 != 0 || d->in_mode != RDQ_IN_PLAIN || d->cout < 1 || d->cout > IG_BN || d->kh != d->kw ||
-        (d->kh != 7 && d->kh != 3) || d->pad < 0 || d->H < 1 || d->W < 1 || cc_ok(d))
+    if (!conv_in_ok(d, x, nullptr) || !w || !y || !t || !w1 || !b1 || !w2 || !b2 || !temb || d->cin2 != 0 ||
+        d->in_mode != RDQ_IN_PLAIN || d->cout > IG_BN || d->kh != d->kw || (d->kh != 7 && d->kh != 3) || cc_ok(d))
         return RDQ_E_INVALID;
     if (dim < 4 || dim % 2 || hid < 1 || out < 1 || dim + hid > IG_SMEM) return RDQ_E_INVALID;
     IgArgs a{};
@@ -3910,9 +3972,7 @@ int rdq_unet_head(const rdq_conv_desc *d, const float *x, const float *w, const 
     if (ig_splits(d, (size_t)-1 / 2, &per) != 1) return RDQ_E_INVALID;    // rdq_conv2d would split K
     a.S = 1;
     a.per_split = a.nsteps;
-    const int half = dim / 2;
-    const float emb = (float)(std::log((double)theta) / (double)(half - 1));   // python float math
-    const TmArgs m{dim, hid, out, -emb, t, w1, b1, w2, b2, temb};
+    const TmArgs m{dim, hid, out, -sinusoidal_step(dim, theta), t, w1, b1, w2, b2, temb};
     const int gxc = (a.M + IG_BM - 1) / IG_BM, tm_x = (out + TM_ROWS - 1) / TM_ROWS;
     const dim3 grid(gxc + tm_x * d->B);
     if (d->kh == 7) hipLaunchKernelGGL(HIP_KERNEL_NAME(k_unet_head<7>), grid, dim3(256), 0, st, a, gxc, m, tm_x);
@@ -3924,23 +3984,13 @@ int rdq_unet_head(const rdq_conv_desc *d, const float *x, const float *w, const 
 int rdq_conv2d_rms(const rdq_conv_desc *d, const float *x, const float *g, const float *w, const float *bias,
                    const float *residual, float *y, void *ws, size_t ws_bytes, uint32_t *tickets, hipStream_t st)
 {
-    if (!d || !x || !g || !w || !y || !cc_ok(d) || d->kh != 1 || d->in_mode != RDQ_IN_PLAIN || d->cin2 != 0 ||
-        d->cin1 > 2048)
+    if (!conv_in_ok(d, x, nullptr) || !g || !w || !y || !cc_ok(d) || d->kh != 1 || d->in_mode != RDQ_IN_PLAIN ||
+        d->cin2 != 0 || d->cin1 > 2048)
         return RDQ_E_INVALID;
-    CcArgs c{};
-    c.d = *d; c.x = x; c.x2 = nullptr; c.w = w; c.bias = bias; c.res = residual; c.y = y;
-    c.part = static_cast<float *>(ws);
-    c.tickets = tickets;
+    CcArgs c = cc_args(d, ws, ws_bytes, tickets, CC_SPLIT_FOLD);     // no k_conv_reduce pass here
+    c.x = x; c.w = w; c.bias = bias; c.res = residual; c.y = y;
     c.rms_g = g;
-    c.K = d->cin1;
-    c.HW = d->H * d->W;
-    c.M = d->B * c.HW;
-    cc_extents(c, d);
-    c.nstages = d->cin1 / CcCfg<1>::CPS;
-    c.S = (ws && tickets) ? cc_splits(d, ws_bytes, &c.per_split) : 1;
-    if (c.S == 1) c.per_split = c.nstages;
-    const dim3 grid((c.M + CC_BM - 1) / CC_BM, (d->cout + CC_BN - 1) / CC_BN, c.S);
-    hipLaunchKernelGGL(HIP_KERNEL_NAME(k_conv_cc<1, RDQ_IN_PLAIN, true>), grid, dim3(256), 0, st, c);
+    hipLaunchKernelGGL(HIP_KERNEL_NAME(k_conv_cc<1, RDQ_IN_PLAIN, true>), cc_grid(c), dim3(256), 0, st, c);
     RDQ_CHECK(hipGetLastError());
     return 0;
 }
@@ -3995,7 +4045,7 @@ int rdq_unet_options_generation(void) { return g_opt_gen.load(); }
 
 int rdq_conv2d_stem(const rdq_conv_desc *d, const float *x, const float *w, const float *bias, float *y, hipStream_t st)
 {
-    if (!conv_desc_ok(d) || !x || !w || !y || d->cin1 != 1 || d->cin2 != 0 || d->kh != ST_K || d->kw != ST_K ||
+    if (!conv_in_ok(d, x, nullptr) || !w || !y || d->cin1 != 1 || d->cin2 != 0 || d->kh != ST_K || d->kw != ST_K ||
         d->pad != ST_K / 2 || d->cout != ST_C || d->in_mode != RDQ_IN_PLAIN || d->W < 64 || d->W > C3_WMAX ||
         (int64_t)d->B * ST_C * d->H * d->W >= ((int64_t)1 << 31))
         return RDQ_E_INVALID;
@@ -4010,23 +4060,11 @@ int rdq_conv2d_stem(const rdq_conv_desc *d, const float *x, const float *w, cons
 int rdq_conv2d_bf16(const rdq_conv_desc *d, const float *x, const float *x2, const void *wp, const float *bias,
                     const float *residual, float *y, void *ws, size_t ws_bytes, hipStream_t st)
 {
-    if (!conv_desc_ok(d) || !x || !wp || !y || (d->cin2 > 0 && !x2 && d->in_mode == RDQ_IN_PLAIN))
-        return RDQ_E_INVALID;
+    if (!conv_in_ok(d, x, x2) || !wp || !y) return RDQ_E_INVALID;
     if (conv3_ok(d) && !g_bf16_per_tap) {
-        C3Args c{};
-        c.d = *d; c.x = x; c.x2 = x2; c.w = static_cast<const __bf16 *>(wp); c.bias = bias; c.res = residual; c.y = y;
-        c.cinp = bf_cinp(d);
-        c.K = 9 * c.cinp;
-        c.HW = d->H * d->W;
-        c.M = d->B * c.HW;
-        c.R = C3_BM + 2 * d->W + 2;
-        c.cch = c.cinp / BF_BK;
-        c.plane = d->in_mode == RDQ_IN_UPSAMPLE2 ? c.HW / 4 : c.HW;
-        const dim3 grid((c.M + C3_BM - 1) / C3_BM, d->cout / C3_BN);
-        if (d->in_mode == RDQ_IN_UPSAMPLE2)
-            hipLaunchKernelGGL(HIP_KERNEL_NAME(k_conv3_bf16<RDQ_IN_UPSAMPLE2>), grid, dim3(256), 0, st, c);
-        else
-            hipLaunchKernelGGL(HIP_KERNEL_NAME(k_conv3_bf16<RDQ_IN_PLAIN>), grid, dim3(256), 0, st, c);
+        C3Args c = c3_args(d, BF_BK);
+        c.x = x; c.x2 = x2; c.w = static_cast<const __bf16 *>(wp); c.bias = bias; c.res = residual; c.y = y;
+        launch_conv3_bf16(c, false, st);
         RDQ_CHECK(hipGetLastError());
         return 0;
     }
@@ -4044,11 +4082,7 @@ int rdq_conv2d_bf16(const rdq_conv_desc *d, const float *x, const float *x2, con
     const dim3 grid((a.M + BF_BM - 1) / BF_BM, (d->cout + 32 * NB - 1) / (32 * NB), a.S);
     if (NB == 4) launch_conv_bf16<4>(grid, st, a);
     else launch_conv_bf16<2>(grid, st, a);
-    if (a.S > 1) {
-        const int64_t total = (int64_t)a.M * d->cout;
-        hipLaunchKernelGGL(k_conv_reduce, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, st, a.S, total, d->cout,
-                           a.HW, a.part, bias, residual, y);
-    }
+    if (a.S > 1) launch_conv_reduce(a.S, d, a.part, bias, residual, y, st);
     RDQ_CHECK(hipGetLastError());
     return 0;
 }
@@ -4062,44 +4096,34 @@ size_t rdq_conv2d_bf16_gn_ws_bytes(const rdq_conv_desc *d, int32_t G)
     return M * d->cout * sizeof(float) + mt * G * 4 * sizeof(double);
 }
 
-int rdq_conv2d_bf16_gn_silu(const rdq_conv_desc *d, const float *x, const float *x2, const void *wp, const float *bias,
-                            int32_t G, float eps, const float *gamma, const float *beta, const float *scale_shift,
-                            const float *post_residual, float *y, void *ws, size_t ws_bytes, hipStream_t st);
-
 // conv3x3_bf16 + GroupNorm statistics in its epilogue (as rdq_conv2d_bf16_gn_silu), conv output in ws
 static bool bf16_gn_conv(const rdq_conv_desc *d, const float *x, const float *x2, const void *wp, const float *bias,
                          int32_t G, void *ws, size_t ws_bytes, C3Args &c, hipStream_t st, const void *x8 = nullptr)
 {
     const size_t need = rdq_conv2d_bf16_gn_ws_bytes(d, G);
-    if (!need || !(x || x8) || !wp || !ws || ws_bytes < need || (d->cin2 > 0 && !x2 && d->in_mode == RDQ_IN_PLAIN))
-        return false;
+    if (!need || !conv_in_ok(d, x8 ? x8 : x, x2) || !wp || !ws || ws_bytes < need) return false;
     // packed bf16 octet input: plain mode, one input tensor, channel count a multiple of the 32-deep chunk
     if (x8 && (d->in_mode != RDQ_IN_PLAIN || d->cin2 != 0 || d->cin1 % BF_BK ||
                (int64_t)d->B * d->cin1 * d->H * d->W >= ((int64_t)1 << 32)))
         return false;
     const size_t M = (size_t)d->B * d->H * d->W;
     float *h = static_cast<float *>(ws);
-    c = C3Args{};
-    c.d = *d; c.x = x; c.x2 = x2; c.w = static_cast<const __bf16 *>(wp); c.bias = bias; c.res = nullptr; c.y = h;
+    c = c3_args(d, BF_BK);
+    c.x = x; c.x2 = x2; c.w = static_cast<const __bf16 *>(wp); c.bias = bias; c.y = h;
     c.yb = C3_BF16_RAW ? reinterpret_cast<__bf16 *>(h) : nullptr;   // raw conv output held as bf16
     c.gnp = reinterpret_cast<double *>(h + M * d->cout);
     c.G = G;
-    c.cinp = bf_cinp(d);
-    c.K = 9 * c.cinp;
-    c.HW = d->H * d->W;
-    c.M = (int)M;
-    c.R = C3_BM + 2 * d->W + 2;
-    c.cch = c.cinp / BF_BK;
-    c.plane = d->in_mode == RDQ_IN_UPSAMPLE2 ? c.HW / 4 : c.HW;
     c.x8 = static_cast<const __bf16 *>(x8);
-    const dim3 grid((c.M + C3_BM - 1) / C3_BM, d->cout / C3_BN);
-    if (x8)
-        hipLaunchKernelGGL(HIP_KERNEL_NAME(k_conv3_bf16<RDQ_IN_PLAIN, true>), grid, dim3(256), 0, st, c);
-    else if (d->in_mode == RDQ_IN_UPSAMPLE2)
-        hipLaunchKernelGGL(HIP_KERNEL_NAME(k_conv3_bf16<RDQ_IN_UPSAMPLE2>), grid, dim3(256), 0, st, c);
-    else
-        hipLaunchKernelGGL(HIP_KERNEL_NAME(k_conv3_bf16<RDQ_IN_PLAIN>), grid, dim3(256), 0, st, c);
+    launch_conv3_bf16(c, x8 != nullptr, st);
     return true;
+}
+
+// the normalise pass of a bf16_gn_conv Block: on the conv output as it is held, bf16 or fp32
+static void bf16_gn_apply(const C3Args &c, int32_t G, float eps, const float *gamma, const float *beta,
+                          const float *scale_shift, const float *post_residual, float *y, hipStream_t st)
+{
+    if (c.yb) launch_gn_apply_t(&c.d, G, c.yb, gamma, beta, scale_shift, c.gnp, eps, post_residual, y, C3_BM, st);
+    else launch_gn_apply_t(&c.d, G, c.y, gamma, beta, scale_shift, c.gnp, eps, post_residual, y, C3_BM, st);
 }
 
 int rdq_conv2d_bf16_gn_silu8(const rdq_conv_desc *d, const float *x, const float *x2, const void *wp,
@@ -4131,16 +4155,7 @@ int rdq_conv2d_bf16_gn_silu_x8(const rdq_conv_desc *d, const void *x8, const voi
     C3Args c;
     if (!y || !gamma || !beta || !x8 || !bf16_gn_conv(d, nullptr, nullptr, wp, bias, G, ws, ws_bytes, c, st, x8))
         return RDQ_E_INVALID;
-    const int C = d->cout, HW = c.HW;
-    int nch = 0;
-    bool gn4 = false;
-    const int gxa = gn_grid(d->B, C, G, HW, &nch, &gn4);
-    if (c.yb)
-        LAUNCH_GN_TB(dim3(gxa, d->B * G), st, C, HW, G, nch, c.yb, gamma, beta, scale_shift, c.gnp, eps, post_residual, y,
-                     C3_BM);
-    else
-        LAUNCH_GN_T(dim3(gxa, d->B * G), st, C, HW, G, nch, c.y, gamma, beta, scale_shift, c.gnp, eps, post_residual, y,
-                    C3_BM);
+    bf16_gn_apply(c, G, eps, gamma, beta, scale_shift, post_residual, y, st);
     RDQ_CHECK(hipGetLastError());
     return 0;
 }
@@ -4151,16 +4166,7 @@ int rdq_conv2d_bf16_gn_silu(const rdq_conv_desc *d, const float *x, const float 
 {
     C3Args c;
     if (!y || !gamma || !beta || !bf16_gn_conv(d, x, x2, wp, bias, G, ws, ws_bytes, c, st)) return RDQ_E_INVALID;
-    const int C = d->cout, HW = c.HW;
-    int nch = 0;
-    bool gn4 = false;
-    const int gxa = gn_grid(d->B, C, G, HW, &nch, &gn4);
-    if (c.yb)
-        LAUNCH_GN_TB(dim3(gxa, d->B * G), st, C, HW, G, nch, c.yb, gamma, beta, scale_shift, c.gnp, eps, post_residual, y,
-                     C3_BM);
-    else
-        LAUNCH_GN_T(dim3(gxa, d->B * G), st, C, HW, G, nch, c.y, gamma, beta, scale_shift, c.gnp, eps, post_residual, y,
-                    C3_BM);
+    bf16_gn_apply(c, G, eps, gamma, beta, scale_shift, post_residual, y, st);
     RDQ_CHECK(hipGetLastError());
     return 0;
 }
@@ -4175,13 +4181,9 @@ int rdq_conv2d_bf16_gn_silu_out(const rdq_conv_desc *d, const float *x, const fl
         !bf16_gn_conv(d, x, x2, wp, bias, G, ws, ws_bytes, c, st))
         return RDQ_E_INVALID;
     if (c.yb)
-        hipLaunchKernelGGL(HIP_KERNEL_NAME(k_gn_apply_out<__bf16>), dim3((c.HW + 63) / 64, d->B), dim3(64 * GO_NW), 0, st,
-                           d->cout, c.HW, G, c.yb, gamma, beta, scale_shift, c.gnp, eps, post_residual, nf, wf, bf, yf,
-                           C3_BM);
+        launch_gn_apply_out(d, G, c.yb, gamma, beta, scale_shift, c.gnp, eps, post_residual, nf, wf, bf, yf, C3_BM, st);
     else
-        hipLaunchKernelGGL(HIP_KERNEL_NAME(k_gn_apply_out<float>), dim3((c.HW + 63) / 64, d->B), dim3(64 * GO_NW), 0, st,
-                           d->cout, c.HW, G, c.y, gamma, beta, scale_shift, c.gnp, eps, post_residual, nf, wf, bf, yf,
-                           C3_BM);
+        launch_gn_apply_out(d, G, c.y, gamma, beta, scale_shift, c.gnp, eps, post_residual, nf, wf, bf, yf, C3_BM, st);
     RDQ_CHECK(hipGetLastError());
     return 0;
 }
@@ -4209,8 +4211,13 @@ int rdq_group_norm_silu(int32_t B, int32_t C, int32_t HW, int32_t G, float eps, 
     const bool sep = blocks > 4096;                    // a separate statistics pass pays off
     if (sep)
         hipLaunchKernelGGL(k_gn_stats, dim3((B * G + 255) / 256), dim3(256), 0, st, B * G, nchunk, gsize, eps, part, stat);
-    LAUNCH_GN(dim3(gxa, B * G), st, C, HW, G, nch, x, gamma, beta, ss,
-                       sep ? stat : nullptr, part, nchunk, eps, y);
+    const float *stats = sep ? stat : nullptr;
+    if (nch < 0)      // the small-image form
+        hipLaunchKernelGGL(HIP_KERNEL_NAME(k_gn_apply<true>), dim3(gxa, B * G), dim3(256), 0, st, C, HW, G, nch, x, gamma,
+                           beta, ss, stats, part, nchunk, eps, y);
+    else
+        hipLaunchKernelGGL(HIP_KERNEL_NAME(k_gn_apply<false>), dim3(gxa, B * G), dim3(256), 0, st, C, HW, G, nch, x, gamma,
+                           beta, ss, stats, part, nchunk, eps, y);
     RDQ_CHECK(hipGetLastError());
     return 0;
 }
@@ -4239,9 +4246,7 @@ int rdq_linear(int32_t B, int32_t in, int32_t out, const float *x, const float *
 int rdq_sinusoidal_emb(int32_t B, int32_t dim, float theta, const int64_t *t, float *y, hipStream_t st)
 {
     if (B < 1 || dim < 4 || dim % 2 || dim > 2048 || !t || !y) return RDQ_E_INVALID;
-    const int half = dim / 2;
-    const float emb = (float)(std::log((double)theta) / (double)(half - 1));   // python float math
-    hipLaunchKernelGGL(k_sinusoidal, dim3(B), dim3(half), 0, st, dim, -emb, t, y);
+    hipLaunchKernelGGL(k_sinusoidal, dim3(B), dim3(dim / 2), 0, st, dim, -sinusoidal_step(dim, theta), t, y);
     RDQ_CHECK(hipGetLastError());
     return 0;
 }
@@ -4252,9 +4257,7 @@ int rdq_time_mlp(int32_t B, int32_t dim, float theta, const int64_t *t, const fl
     if (B < 1 || dim < 4 || dim % 2 || hid < 1 || out < 1 || (size_t)(dim + hid) * 4 * TMB > 64 * 1024 ||
         !t || !w1 || !b1 || !w2 || !b2 || !y)
         return RDQ_E_INVALID;
-    const int half = dim / 2;
-    const float emb = (float)(std::log((double)theta) / (double)(half - 1));   // python float math
-    const TmArgs m{dim, hid, out, -emb, t, w1, b1, w2, b2, y};
+    const TmArgs m{dim, hid, out, -sinusoidal_step(dim, theta), t, w1, b1, w2, b2, y};
     if (B > 2 * TMB)
         hipLaunchKernelGGL(k_time_mlp_b, dim3((out + 4 * TMB_RW - 1) / (4 * TMB_RW), (B + TMB - 1) / TMB), dim3(256),
                            TMB * (dim + hid) * sizeof(float), st, m, B);
@@ -4268,18 +4271,9 @@ int rdq_time_mlp(int32_t B, int32_t dim, float theta, const int64_t *t, const fl
 int rdq_linear_silu_multi(int32_t B, int32_t in, const float *x, int32_t n, const float *const *w,
                           const float *const *b, const int32_t *out, float *const *y, hipStream_t st)
 {
-    if (B < 1 || in < 1 || !x || n < 1 || n > LM_MAX || !w || !out || !y) return RDQ_E_INVALID;
-    LinMulti L{};
-    L.n = n;
-    L.start[0] = 0;
-    for (int j = 0; j < n; ++j) {
-        if (!w[j] || !y[j] || out[j] < 1) return RDQ_E_INVALID;
-        L.w[j] = w[j];
-        L.b[j] = b ? b[j] : nullptr;
-        L.y[j] = y[j];
-        L.out[j] = out[j];
-        L.start[j + 1] = L.start[j] + out[j];
-    }
+    LinMulti L;
+    if (B < 1 || in < 1 || !x || n < 1 || n > LM_MAX || !w || !out || !y || !lin_multi(L, n, w, b, out, y))
+        return RDQ_E_INVALID;
     if (B > LSB / 2 && in == 256)
         hipLaunchKernelGGL(k_wdot_silu_b, dim3((L.start[n] + 4 * WDR - 1) / (4 * WDR), (B + 63) / 64), dim3(256), 0, st, B,
                            x, L);
@@ -4294,6 +4288,21 @@ int rdq_linear_silu_multi(int32_t B, int32_t in, const float *x, int32_t n, cons
 
 static int la_chunks(int n, int nmem) { return (n + nmem + LA_CH - 1) / LA_CH; }
 
+// the areas of rdq_linear_attention_ws_bytes: per-chunk k statistics, partial contexts, the combined context
+struct LaWs {
+    int nch;
+    float *pstat, *part, *ctx;
+};
+static LaWs la_ws(void *ws, int B, int heads, int dh, int n, int nmem)
+{
+    LaWs a;
+    a.nch = la_chunks(n, nmem);
+    a.pstat = static_cast<float *>(ws);
+    a.part = a.pstat + (size_t)a.nch * B * heads * dh * 2;
+    a.ctx = a.part + (size_t)a.nch * B * heads * dh * dh;
+    return a;
+}
+
 size_t rdq_linear_attention_ws_bytes(int32_t B, int32_t heads, int32_t dh, int32_t n, int32_t nmem)
 {
     if (B < 1 || heads < 1 || dh < 1 || n < 1 || nmem < 0) return 0;
@@ -4306,14 +4315,11 @@ int rdq_linear_attention(int32_t B, int32_t heads, int32_t dh, int32_t n, int32_
 {
     if (B < 1 || heads < 1 || dh < 1 || dh > 32 || n < 1 || nmem < 0 || !qkv || !mem_kv || !out || !ws)
         return RDQ_E_INVALID;
-    const int nch = la_chunks(n, nmem);
-    float *pstat = (float *)ws;
-    float *part = pstat + (size_t)nch * B * heads * dh * 2;
-    float *ctx = part + (size_t)nch * B * heads * dh * dh;
-    hipLaunchKernelGGL(k_la_ctx, dim3(nch, heads, B), dim3(256), 0, st, heads, dh, n, nmem, qkv, mem_kv, part, pstat);
+    const LaWs a = la_ws(ws, B, heads, dh, n, nmem);
+    hipLaunchKernelGGL(k_la_ctx, dim3(a.nch, heads, B), dim3(256), 0, st, heads, dh, n, nmem, qkv, mem_kv, a.part, a.pstat);
     const int bhdd = B * heads * dh * dh;
-    hipLaunchKernelGGL(k_la_reduce, dim3((bhdd + 255) / 256), dim3(256), 0, st, bhdd, dh, nch, pstat, part, ctx);
-    hipLaunchKernelGGL(k_la_out, dim3((n + 63) / 64, heads, B), dim3(256), 0, st, heads, dh, n, scale, qkv, ctx,
+    hipLaunchKernelGGL(k_la_reduce, dim3((bhdd + 255) / 256), dim3(256), 0, st, bhdd, dh, a.nch, a.pstat, a.part, a.ctx);
+    hipLaunchKernelGGL(k_la_out, dim3((n + 63) / 64, heads, B), dim3(256), 0, st, heads, dh, n, scale, qkv, a.ctx,
                        out);
     RDQ_CHECK(hipGetLastError());
     return 0;
@@ -4327,116 +4333,43 @@ int rdq_linear_attention_block(int32_t B, int32_t heads, int32_t dh, int32_t n, 
     if (B < 1 || heads != 4 || dh != 32 || n < 1 || nmem < 0 || !qkv || !mem_kv || !w_out || !g_out ||
         !y || !ws || (dim != 64 && dim != 128 && dim != 256))
         return RDQ_E_INVALID;
-    const int nch = la_chunks(n, nmem);
-    float *pstat = (float *)ws;
-    float *part = pstat + (size_t)nch * B * heads * dh * 2;
-    float *ctx = part + (size_t)nch * B * heads * dh * dh;
-    hipLaunchKernelGGL(k_la_ctx, dim3(nch, heads, B), dim3(256), 0, st, heads, dh, n, nmem, qkv, mem_kv, part, pstat);
-    int fold = nch;
-    const float *src = part;
-    if (nch > LAO_MAXCH) {          // many chunks (72 x 72): the combine keeps its own launch
+    const LaWs a = la_ws(ws, B, heads, dh, n, nmem);
+    hipLaunchKernelGGL(k_la_ctx, dim3(a.nch, heads, B), dim3(256), 0, st, heads, dh, n, nmem, qkv, mem_kv, a.part, a.pstat);
+    int fold = a.nch;
+    const float *src = a.part;
+    if (a.nch > LAO_MAXCH) {        // many chunks (72 x 72): the combine keeps its own launch
         const int bhdd = B * heads * dh * dh;
-        hipLaunchKernelGGL(k_la_reduce, dim3((bhdd + 255) / 256), dim3(256), 0, st, bhdd, dh, nch, pstat, part, ctx);
+        hipLaunchKernelGGL(k_la_reduce, dim3((bhdd + 255) / 256), dim3(256), 0, st, bhdd, dh, a.nch, a.pstat, a.part, a.ctx);
         fold = 0;
-        src = ctx;
+        src = a.ctx;
     }
-    if (dim == 64) launch_la_out_proj<64>(B, heads, n, fold, scale, qkv, pstat, src, w_out, b_out, g_out, res, y, st);
-    else if (dim == 128) launch_la_out_proj<128>(B, heads, n, fold, scale, qkv, pstat, src, w_out, b_out, g_out, res, y, st);
-    else launch_la_out_proj<256>(B, heads, n, fold, scale, qkv, pstat, src, w_out, b_out, g_out, res, y, st);
+    if (dim == 64) launch_la_out_proj<64>(B, heads, n, fold, scale, qkv, a.pstat, src, w_out, b_out, g_out, res, y, st);
+    else if (dim == 128) launch_la_out_proj<128>(B, heads, n, fold, scale, qkv, a.pstat, src, w_out, b_out, g_out, res, y, st);
+    else launch_la_out_proj<256>(B, heads, n, fold, scale, qkv, a.pstat, src, w_out, b_out, g_out, res, y, st);
     RDQ_CHECK(hipGetLastError());
     return 0;
 }
 
-// rdq_linear_attention_bf16: pixel chunks of nsub 64-pixel tiles, about 2048 workgroups per launch
-static void lab_split(int B, int n, int *nsub, int *nch)
-{
-    const int tiles = (n + LB_PX - 1) / LB_PX;
-    int s = (int)std::min<int64_t>(16, std::max<int64_t>(2, ((int64_t)tiles * B + 2047) / 2048));
-    s = std::min(s, tiles);
-    *nsub = s;
-    *nch = (tiles + s - 1) / s;
-}
-
-size_t rdq_linear_attention_bf16_ws_bytes(int32_t B, int32_t dim, int32_t n)
-{
-    if (B < 1 || n < 1 || (dim != 64 && dim != 128)) return 0;
-    int nsub, nch;
-    lab_split(B, n, &nsub, &nch);
-    return (size_t)B * nch * LB_PART * sizeof(float);
-}
+size_t rdq_linear_attention_bf16_ws_bytes(int32_t B, int32_t dim, int32_t n) { return lab_ws_bytes<false>(B, dim, n); }
 
 int rdq_linear_attention_bf16(int32_t B, int32_t dim, int32_t n, int32_t nmem, float scale, const float *x,
                               const float *g_in, const void *wqkv, const float *mem_kv, const void *wout,
                               const float *b_out, const float *g_out, float *y, void *ws, size_t ws_bytes,
                               hipStream_t st)
 {
-    if (B < 1 || n < 1 || nmem < 0 || (dim != 64 && dim != 128) || !x || !g_in || !wqkv ||
-        (nmem > 0 && !mem_kv) || !wout || !g_out || !y || !ws || y == x)
-        return RDQ_E_INVALID;
-    if ((int64_t)B * dim * n >= ((int64_t)1 << 31) || ws_bytes < rdq_linear_attention_bf16_ws_bytes(B, dim, n))
-        return RDQ_E_INVALID;
-    LabArgs a{};
-    a.x = x; a.g_in = g_in; a.mem = mem_kv; a.b_out = b_out; a.g_out = g_out;
-    a.wqkv = static_cast<const __bf16 *>(wqkv); a.wout = static_cast<const __bf16 *>(wout);
-    a.part = static_cast<float *>(ws); a.y = y;
-    a.n = n; a.nmem = nmem; a.scale = scale;
-    lab_split(B, n, &a.nsub, &a.nch);
-    const dim3 grid(a.nch, B);
-    if (dim == 64) {
-        hipLaunchKernelGGL(k_lab_kv<64>, grid, dim3(256), 0, st, a);
-        hipLaunchKernelGGL(k_lab_out<64>, grid, dim3(256), 0, st, a);
-    } else {
-        hipLaunchKernelGGL(k_lab_kv<128>, grid, dim3(256), 0, st, a);
-        hipLaunchKernelGGL(k_lab_out<128>, grid, dim3(256), 0, st, a);
-    }
-    RDQ_CHECK(hipGetLastError());
-    return 0;
+    return linear_attention_fused<false>(B, dim, n, nmem, scale, x, g_in, wqkv, mem_kv, wout, b_out, g_out, y, ws,
+                                         ws_bytes, st);
 }
 
-// the fp32 form: WGs for about 1024 subtiles (small batches: the combine reads every chunk's partials)
-static void lab_split32(int B, int n, int *nsub, int *nch)
-{
-    const int tiles = (n + LB_PX - 1) / LB_PX;
-    int s_ = (int)std::min<int64_t>(16, std::max<int64_t>(1, ((int64_t)tiles * B + 1023) / 1024));
-    s_ = std::min(s_, tiles);
-    *nsub = s_;
-    *nch = (tiles + s_ - 1) / s_;
-}
-
-size_t rdq_linear_attention_f32_ws_bytes(int32_t B, int32_t dim, int32_t n)
-{
-    if (B < 1 || n < 1 || (dim != 64 && dim != 128)) return 0;
-    int nsub, nch;
-    lab_split32(B, n, &nsub, &nch);
-    return (size_t)B * nch * LB_PART * sizeof(float);
-}
+size_t rdq_linear_attention_f32_ws_bytes(int32_t B, int32_t dim, int32_t n) { return lab_ws_bytes<true>(B, dim, n); }
 
 int rdq_linear_attention_f32(int32_t B, int32_t dim, int32_t n, int32_t nmem, float scale, const float *x,
                              const float *g_in, const float *wqkv, const float *mem_kv, const float *wout,
                              const float *b_out, const float *g_out, float *y, void *ws, size_t ws_bytes,
                              hipStream_t st)
 {
-    if (B < 1 || n < 1 || nmem < 0 || (dim != 64 && dim != 128) || !x || !g_in || !wqkv ||
-        (nmem > 0 && !mem_kv) || !wout || !g_out || !y || !ws || y == x)
-        return RDQ_E_INVALID;
-    if ((int64_t)B * dim * n >= ((int64_t)1 << 31) || ws_bytes < rdq_linear_attention_f32_ws_bytes(B, dim, n))
-        return RDQ_E_INVALID;
-    LabArgs a{};
-    a.x = x; a.g_in = g_in; a.mem = mem_kv; a.b_out = b_out; a.g_out = g_out;
-    a.wqkv32 = wqkv; a.wout32 = wout;
-    a.part = static_cast<float *>(ws); a.y = y;
-    a.n = n; a.nmem = nmem; a.scale = scale;
-    lab_split32(B, n, &a.nsub, &a.nch);
-    const dim3 grid(a.nch, B);
-    if (dim == 64) {
-        hipLaunchKernelGGL(HIP_KERNEL_NAME(k_lab_kv<64, true>), grid, dim3(256), 0, st, a);
-        hipLaunchKernelGGL(HIP_KERNEL_NAME(k_lab_out<64, true>), grid, dim3(256), 0, st, a);
-    } else {
-        hipLaunchKernelGGL(HIP_KERNEL_NAME(k_lab_kv<128, true>), grid, dim3(256), 0, st, a);
-        hipLaunchKernelGGL(HIP_KERNEL_NAME(k_lab_out<128, true>), grid, dim3(256), 0, st, a);
-    }
-    RDQ_CHECK(hipGetLastError());
-    return 0;
+    return linear_attention_fused<true>(B, dim, n, nmem, scale, x, g_in, wqkv, mem_kv, wout, b_out, g_out, y, ws,
+                                        ws_bytes, st);
 }
 
 int rdq_full_attention(int32_t B, int32_t heads, int32_t dh, int32_t n, int32_t nmem, const float *qkv,
@@ -4451,24 +4384,27 @@ int rdq_full_attention(int32_t B, int32_t heads, int32_t dh, int32_t n, int32_t 
     return 0;
 }
 
-int rdq_red_q_sample(int32_t B, int64_t n, const float *sa, const float *s1a, const int64_t *t, const float *x0,
-                     const float *eps, float *xt, hipStream_t st)
+// t_out null: rdq_red_q_sample
+static int red_q_sample(int32_t B, int64_t n, const float *sa, const float *s1a, const int64_t *t, const float *x0,
+                        const float *eps, float *xt, int64_t *t_out, hipStream_t st)
 {
     if (B < 1 || n < 1 || !sa || !s1a || !t || !x0 || !eps || !xt) return RDQ_E_INVALID;
     hipLaunchKernelGGL(k_red_q_sample, dim3((unsigned)((n + 255) / 256), B), dim3(256), 0, st, n, sa, s1a, t, x0, eps, xt,
-                       (int64_t *)nullptr);
+                       t_out);
     RDQ_CHECK(hipGetLastError());
     return 0;
+}
+
+int rdq_red_q_sample(int32_t B, int64_t n, const float *sa, const float *s1a, const int64_t *t, const float *x0,
+                     const float *eps, float *xt, hipStream_t st)
+{
+    return red_q_sample(B, n, sa, s1a, t, x0, eps, xt, nullptr, st);
 }
 
 int rdq_red_q_sample_t(int32_t B, int64_t n, const float *sa, const float *s1a, const int64_t *t, const float *x0,
                        const float *eps, float *xt, int64_t *t_out, hipStream_t st)
 {
-    if (B < 1 || n < 1 || !sa || !s1a || !t || !x0 || !eps || !xt || !t_out) return RDQ_E_INVALID;
-    hipLaunchKernelGGL(k_red_q_sample, dim3((unsigned)((n + 255) / 256), B), dim3(256), 0, st, n, sa, s1a, t, x0, eps, xt,
-                       t_out);
-    RDQ_CHECK(hipGetLastError());
-    return 0;
+    return t_out ? red_q_sample(B, n, sa, s1a, t, x0, eps, xt, t_out, st) : RDQ_E_INVALID;
 }
 
 int rdq_red_epilogue(int32_t B, int64_t n, const float *sr, const float *srm1, const int64_t *t, const float *xt,

@@ -130,6 +130,29 @@ def test_conv_gn_silu_fused(cuda, cin1, cin2, cout, H, B, ss, post):
     assert int(O._TICKET_POOL[x.device]["pool"].abs().sum()) == 0
 
 
+def test_conv_gn_silu_fused_without_tickets(cuda, monkeypatch):
+    """The fused Block when the caller has no arrival tickets (the first call inside a graph capture, or
+    the graph region of the pool used up): the epilogue statistics need the in-launch combine, so the
+    conv must then not split K at all, and the result keeps the fp32 bar (same products, another
+    summation order).  512 + 256 -> 512 channels at 9 x 9, B = 1 is the smallest of the U-Net's shapes
+    whose conv splits K when it has tickets (24 tiles, 96 K stages)."""
+    from red_diffeq import ops as O
+    from red_diffeq.models import unet_ops as ops
+    torch.manual_seed(6)
+    conv = nn.Conv2d(768, 512, 3, padding=1).to(cuda)
+    norm = nn.GroupNorm(8, 512).to(cuda)
+    x = torch.randn(1, 512, 9, 9, device=cuda)
+    x2 = torch.randn(1, 256, 9, 9, device=cuda)
+    sc = torch.randn(1, 1024, device=cuda)
+    with torch.no_grad():
+        with_tickets = ops.conv_group_norm_silu(x, conv, norm, sc, skip=x2)
+        monkeypatch.setattr(O, "_tickets", lambda device, n: None)
+        got = ops.conv_group_norm_silu(x, conv, norm, sc, skip=x2)
+        ref = R.group_norm_affine_silu(R.conv2d(torch.cat((x, x2), 1), conv), norm, sc[:, :, None, None].chunk(2, dim=1))
+    close(got, ref, rel=1e-5, what="no tickets vs torch")
+    close(got, with_tickets, rel=1e-5, what="no tickets vs split K")
+
+
 # ResnetBlock with a 1x1 shortcut: block1's conv and res_conv in one launch (rdq_conv2d_gn_silu_sc),
 # bitwise equal to the separate calls, on the U-Net's up-path / final-block shapes
 @pytest.mark.parametrize("cin1,cin2,cout,H,B", [(512, 256, 512, 9, 1), (256, 128, 256, 18, 1), (128, 64, 128, 36, 2),
