@@ -156,6 +156,18 @@ int rdq_fwi_set_sweep_delay(rdq_fwi_plan *plan, int32_t fwd_ticks, int32_t adj_t
  * mode 0 (rdq_fwi_launch_info reports the mode that runs).  Only the order of independent register and
  * memory operations differs: results are bit-identical in both modes. */
 int rdq_fwi_set_handoff_overlap(rdq_fwi_plan *plan, int32_t fwd_mode, int32_t adj_mode);
+/* Wave roles of the persistent forward and (recurrence) adjoint; 0 = every wave runs the generic time loop:
+ *   adjoint 1 (default): a wave whose rows hold neither the source row nor the receiver row runs every
+ *              epoch but the last in a loop of its own, with the per-step source / receiver /
+ *              end-of-record / history-guard tests compiled out (they are wave-uniform and constant for
+ *              the launch); the other waves, and the last epoch, run the generic loop (configs[1]:
+ *              1.446 -> 1.419 ms);
+ *   forward:   0 only (RDQ_E_INVALID otherwise): the same split of the forward measured no faster.
+ * Mode 1 is built at 4 steps per epoch (the default depth); other depths and the exact-order adjoint run
+ * mode 0 (rdq_fwi_launch_info reports the mode that runs).  The hand-off, the mailbox exchange and every
+ * cell's arithmetic are the same in both modes: results are bit-identical.  Changing the mode drops the
+ * plan's cached graphs. */
+int rdq_fwi_set_wave_roles(rdq_fwi_plan *plan, int32_t fwd_mode, int32_t adj_mode);
 /* 1 (default) = run each time loop as ONE persistent launch (regions resident in registers for
  * all nt steps, epoch-wise neighbour hand-offs) whenever the whole grid fits resident on the
  * device: small surveys (at most 200 workgroups, e.g. 3 OpenFWI shots) in 64 x 64 regions of 16
@@ -182,8 +194,10 @@ int rdq_fwi_set_status_buffer(rdq_fwi_plan *plan, uint32_t *words);
  * rows; 0 = chunked), the same for the adjoint, forward steps per epoch/launch,
  * adjoint steps per epoch/launch, forward time-loop launches per call, adjoint time-loop launches
  * per call (persistent: one per resident shot group; chunked: ceil(nt / T)), the hand-off overlap mode
- * the forward runs, the same for the adjoint (rdq_fwi_set_handoff_overlap; 0 for chunked launches)}. */
-int rdq_fwi_launch_info(rdq_fwi_plan *plan, int32_t B, int32_t out[8]);
+ * the forward runs, the same for the adjoint (rdq_fwi_set_handoff_overlap; 0 for chunked launches), the
+ * wave-role mode the forward runs, the same for the adjoint (rdq_fwi_set_wave_roles; 0 for chunked
+ * launches)}.  `out` holds 10 words (8 before rdq_fwi_set_wave_roles existed). */
+int rdq_fwi_launch_info(rdq_fwi_plan *plan, int32_t B, int32_t out[10]);
 /* The wide chunked kernels' launch shape for batch B: out = {concurrent launch chains, shots per
  * workgroup of the forward's and of the adjoint's full-depth launches of chain 0 (the automatic choice
  * unless rdq_fwi_set_wide_*_shots fixed one), shots in chain 0}. */

@@ -1225,6 +1225,7 @@ __global__ __launch_bounds__(64 * NW) void k_adj_tw(AdjTBArgs a)
 // zeroed before each launch; tag = epoch index (>= 1) so a zeroed granule never matches.
 constexpr int CP_SC1 = 16;                            // buffer cache policy: sc1 (write-through / L1 bypass)
 constexpr int PT_ADJ_SG = 8;                          // adjoint hand-off sweep: rows per load group
+constexpr int PT_ROLES_T = 4;                         // wave roles (rdq_fwi_set_wave_roles) are built at this depth
 constexpr size_t PROF_RAW = 16;                       // per-wave records after the 11 summary words (PT_PROF_FLUSH)
 constexpr size_t PROF_REC = 8;                        // words per wave record
 constexpr size_t PROF_WAVES = 4096 * 16;              // blocks x waves recorded
@@ -1904,6 +1905,7 @@ struct AdjPtArgs {
     int nt, nblk;
     int xcd_mode;
     int sweep_delay;                     // as FwdPtArgs
+    int roles;                           // wave roles: 0 every wave runs the generic loop, 1 plain waves their own
 };
 
 __device__ __forceinline__ float bload_nt(__amdgpu_buffer_rsrc_t r, int voff, int soff)
@@ -2178,8 +2180,8 @@ __global__ __launch_bounds__(64 * NW) void k_adj_pt(AdjPtArgs a)
             u[i] = fma2(-T1v[i], P1[i], P0[i]);                                                     \
             u[i] = fma2(T2v[i], P2[i], u[i]);                                                       \
         }                                                                                           \
-        int sg_ = srow;                              /* one scalar branch for both source terms */  \
-        LAUNDER(sg_);                                                                               \
+        int sg_ = RL_PLAIN ? -1 : srow;              /* one scalar branch for both source terms */  \
+        if constexpr (!RL_PLAIN) LAUNDER(sg_);       /* (plain role: no source row) */              \
         if (sg_ >= 0) {                                                                             \
             int sp_ = spair;                                                                        \
             LAUNDER(sp_);                                                                           \
@@ -2223,8 +2225,8 @@ __global__ __launch_bounds__(64 * NW) void k_adj_pt(AdjPtArgs a)
             const f32x2 nb = fma2(kC3, n2, kC2 * n1);                                               \
             PRV[i] = fma2(T1v[i], CUR[i], fma2(-T2v[i], PRV[i], nb));                               \
         }                                                                                           \
-        int rr_ = (LO) == 0 ? rlo : rhi;             /* the receiver's pair is in this half */      \
-        LAUNDER(rr_);                                                                               \
+        int rr_ = RL_PLAIN ? 0 : (LO) == 0 ? rlo : rhi;   /* the receiver's pair is in this half */ \
+        if constexpr (!RL_PLAIN) LAUNDER(rr_);       /* (plain role: no receiver row) */            \
         if ((HI) > (LO) && rr_ && rec_index(k - 1, g.st) >= 0) {                                    \
             int rp_ = rpair;                                                                        \
             LAUNDER(rp_);                                                                           \
@@ -2234,7 +2236,9 @@ __global__ __launch_bounds__(64 * NW) void k_adj_pt(AdjPtArgs a)
     }
 #define ADJR_STEP_NB(CUR, PRV, P0, P1, P2, PN)                                                      \
     {                                                                                               \
-        if (ldall || (grad && k >= 2)) ADJR_LOAD(PN, HRe, (T - 1 - t) * L4)                         \
+        if constexpr (RL_PLAIN) {                    /* steady epoch: every prefetched slot exists */ \
+            if (grad) ADJR_LOAD(PN, HRe, (T - 1 - t) * L4)                                          \
+        } else if (ldall || (grad && k >= 2)) ADJR_LOAD(PN, HRe, (T - 1 - t) * L4)                  \
         const float dcur = dv[t];                                                                   \
         u32x2 f_;                                                                                   \
         f32x2 E1, E2;                                                                               \
@@ -2246,7 +2250,7 @@ __global__ __launch_bounds__(64 * NW) void k_adj_pt(AdjPtArgs a)
         if (t + 1 < T) xm_put<NW>(xm, (j + 1) & 1, w, lane, (unsigned)j + 2u, A[0] * PRV[0], A[1] * PRV[1]); \
         __builtin_amdgcn_s_setprio(PT_PRIO_BODY);                                                   \
         ADJR_PAIRS_NB(CUR, PRV, 2, RP)                                                              \
-        if (t + 1 < T || last) ADJR_GRAD(CUR, PRV, wv[t], P0, P1, P2)                               \
+        if (t + 1 < T || (!RL_PLAIN && last)) ADJR_GRAD(CUR, PRV, wv[t], P0, P1, P2)                \
     }
 
 // OV (rdq_fwi_set_handoff_overlap): 0 = PT_SWEEP; 1 = the dead cells are zeroed while the sweep's first
@@ -2261,6 +2265,7 @@ __global__ __launch_bounds__(64 * NW) void k_adj_pr(AdjPtArgs a)
     unsigned long long *const prof = PROF ? a.prof : nullptr;   // phase counters: profiled build only
     constexpr bool PT_PRIO = true;                        // wave priorities (PT_PRIO_*)
     constexpr bool PT_MIR = true;                         // mirrored pairs for the exchange's boundary rows
+    constexpr bool RL_PLAIN = false;                      // the generic wave role (shadowed in the plain epochs)
     __shared__ XmBox<NW> xm;                              // the waves' inboxes (xm_*)
     __shared__ double red[64 * NW];
     // the LDS the residency decision (resident_capacity) depends on: the mailboxes and the reduction
@@ -2345,55 +2350,82 @@ __global__ __launch_bounds__(64 * NW) void k_adj_pr(AdjPtArgs a)
     xm_init<NW>(xm, w, lane);                             // no flag matches a tag until written
     __syncthreads();
     xm_put<NW>(xm, 0, w, lane, 1u, f32x2{0.0f, 0.0f}, f32x2{0.0f, 0.0f});   // A L_{nt+1} = 0, step 0's tag
-    for (int e = 0; e < nep; ++e) {
-        const int ke = a.nt - e * T;                      // first step k of this epoch
-        const bool last = e + 1 == nep;
-        const __amdgpu_buffer_rsrc_t HRe = HIST_RSRC(ke);
-        // every step of the epoch prefetches a history slot that exists (k >= 2): one scalar test per
-        // epoch instead of per step (the barrier-free step, ADJR_STEP_NB)
-        int ldall = grad && ke >= T + 1;
-        LAUNDER(ldall);
-#pragma unroll
-        for (int t = 0; t < T; ++t) {
-            const int j = e * T + t;
-            if (j >= a.nt) break;
-            const int k = ke - t;
-            if ((t & 3) == 0) ADJR_STEP_NB(L1, L0, Q0, Q1, Q2, Q3)
-            else if ((t & 3) == 1) ADJR_STEP_NB(L0, L1, Q1, Q2, Q3, Q0)
-            else if ((t & 3) == 2) ADJR_STEP_NB(L1, L0, Q2, Q3, Q0, Q1)
-            else ADJR_STEP_NB(L0, L1, Q3, Q0, Q1, Q2)
-        }
-        if (T & 1) {   // keep "L1 = newest" at every epoch boundary
-#pragma unroll
-            for (int i = 0; i < RP; ++i) { const f32x2 tl = L0[i]; L0[i] = L1[i]; L1[i] = tl; }
-        }
-        // the last step's window (step T - 1: Q[T-1], Q[T], Q[T+1] mod 4), for the deferred gradient
+    int plain = (T == PT_ROLES_T) && a.roles && srow < 0 && rrow < 0;   // wave role, decided once
+    plain = __builtin_amdgcn_readfirstlane(plain);
+// the T steps of one epoch, for the role RL_PLAIN in scope (a plain epoch is steady: all its steps exist)
+#define ADJR_EPOCH_STEPS                                                                            \
+    _Pragma("unroll") for (int t = 0; t < T; ++t) {                                                 \
+        const int j = e * T + t;                                                                    \
+        if (!RL_PLAIN && j >= a.nt) break;                                                          \
+        const int k = ke - t;                                                                       \
+        if ((t & 3) == 0) ADJR_STEP_NB(L1, L0, Q0, Q1, Q2, Q3)                                      \
+        else if ((t & 3) == 1) ADJR_STEP_NB(L0, L1, Q1, Q2, Q3, Q0)                                 \
+        else if ((t & 3) == 2) ADJR_STEP_NB(L1, L0, Q2, Q3, Q0, Q1)                                 \
+        else ADJR_STEP_NB(L0, L1, Q3, Q0, Q1, Q2)                                                   \
+    }
+// the last step's window (step T - 1: Q[T-1], Q[T], Q[T+1] mod 4), for the deferred gradient
 #define QW(o) (((T - 1 + (o)) & 3) == 0 ? Q0 : ((T - 1 + (o)) & 3) == 1 ? Q1 : ((T - 1 + (o)) & 3) == 2 ? Q2 : Q3)
-        PT_PROF(tst)
-        if (!last) {
-            const unsigned tag = (unsigned)(e + 1);
-            const __amdgpu_buffer_rsrc_t GR = rsrc_of(a.gran + (size_t)(2 * ((e + 1) & 1)) * L + 2 * so);
-            PT_PUBLISH(GR, tag, L0, L1)
-            PT_PROF(tpb)
-            const int kn = ke - T;                        // first step k of the next epoch
-            ADJR_GRAD(L0, L1, wv[T - 1], QW(0), QW(1), QW(2))   // the deferred last step (no neighbour data)
-            PT_PROF(tgr)
-            PT_SWEEP_DELAY()
-            if constexpr (OV == 0) PT_SWEEP(GR, tag, L0, L1, PT_ADJ_SG)
-            else PT_SWEEP_SHADOW(GR, tag, L0, L1, PT_ADJ_SG, (PT_ADJ_SG < R ? PT_ADJ_SG : R))
-            // the next step's boundary rows, with the halo cells the sweep reloaded
-            xm_put<NW>(xm, (e + 1) * T & 1, w, lane, (unsigned)((e + 1) * T) + 1u, A[0] * L1[0], A[1] * L1[1]);
+// One epoch e, for the role RL_PLAIN in scope (plain: never the last epoch).  ldall: every step of the
+// epoch prefetches a history slot that exists (k >= 2), one scalar test per epoch instead of per step (the
+// barrier-free step, ADJR_STEP_NB).  After the steps: keep "L1 = newest" at every epoch boundary; publish;
+// the deferred last step's gradient (no neighbour data); the sweep; the next step's boundary rows, with
+// the halo cells the sweep reloaded; restore Q0 = the next epoch's P_k.
+#define ADJR_EPOCH                                                                                  \
+    {                                                                                               \
+        const int ke = a.nt - e * T;                      /* first step k of this epoch */          \
+        const bool last = !RL_PLAIN && e + 1 == nep;                                                \
+        const __amdgpu_buffer_rsrc_t HRe = HIST_RSRC(ke);                                           \
+        int ldall = grad && ke >= T + 1;                                                            \
+        LAUNDER(ldall);                                                                             \
+        ADJR_EPOCH_STEPS                                                                            \
+        if (T & 1) {                                                                                \
+            _Pragma("unroll") for (int i = 0; i < RP; ++i) { const f32x2 tl = L0[i]; L0[i] = L1[i]; L1[i] = tl; } \
+        }                                                                                           \
+        PT_PROF(tst)                                                                                \
+        if (!last) {                                                                                \
+            const unsigned tag = (unsigned)(e + 1);                                                 \
+            const __amdgpu_buffer_rsrc_t GR = rsrc_of(a.gran + (size_t)(2 * ((e + 1) & 1)) * L + 2 * so); \
+            PT_PUBLISH(GR, tag, L0, L1)                                                             \
+            PT_PROF(tpb)                                                                            \
+            const int kn = ke - T;                        /* first step k of the next epoch */      \
+            ADJR_GRAD(L0, L1, wv[T - 1], QW(0), QW(1), QW(2))                                       \
+            PT_PROF(tgr)                                                                            \
+            PT_SWEEP_DELAY()                                                                        \
+            if constexpr (OV == 0) PT_SWEEP(GR, tag, L0, L1, PT_ADJ_SG)                             \
+            else PT_SWEEP_SHADOW(GR, tag, L0, L1, PT_ADJ_SG, (PT_ADJ_SG < R ? PT_ADJ_SG : R))       \
+            xm_put<NW>(xm, (e + 1) * T & 1, w, lane, (unsigned)((e + 1) * T) + 1u, A[0] * L1[0], A[1] * L1[1]); \
+            if constexpr (!RL_PLAIN) ADJ_ISSUE                                                      \
+            PT_PROF_TAIL                                                                            \
+        }                                                                                           \
+        if constexpr ((T & 3) != 0) {                                                               \
+            _Pragma("unroll") for (int i = 0; i < RP; ++i) {                                         \
+                const f32x2 a0 = QW(1)[i], a1 = QW(2)[i], a2 = QW(3)[i], a3 = QW(4)[i];             \
+                Q0[i] = a0; Q1[i] = a1; Q2[i] = a2; Q3[i] = a3;                                     \
+            }                                                                                       \
+        }                                                                                           \
+    }
+    // Wave roles (rdq_fwi_set_wave_roles): a plain wave (no source row, no receiver row) branches once,
+    // here, into a loop of its own over every epoch but the last (steady: all T steps exist, every step's
+    // history prefetch reads an existing slot, the epoch's last gradient is the deferred one), whose steps
+    // carry no per-step source / receiver / j >= nt / last / prefetch test and whose epochs load no wavelet
+    // samples or residuals (they are loaded once, after the loop, for the generic epoch); `grad` stays a
+    // scalar test, so the all-halo waves share that loop.  The generic loop runs the rest: every epoch of
+    // the other waves and the last epoch of all.  Mailbox, publish, sweep, zeroing and tags are the same
+    // text in both, and per cell the arithmetic is the same: results are bit for bit those of mode 0.
+    // configs[1]: 1.4464 -> 1.4193 ms (profiles/r11/kernel_ab_adj_roles.jsonl).  (One loop choosing a body
+    // per epoch spilled 107 VGPRs; the same split of the forward's steps was no faster and is not built.)
+    int e = 0;
+    if constexpr (T == PT_ROLES_T) {
+        if (plain) {
+            constexpr bool RL_PLAIN = true;
+            for (; e + 1 < nep; ++e) ADJR_EPOCH
+            const int kn = a.nt - e * T;                  // the generic epoch's samples and residuals
             ADJ_ISSUE
-            PT_PROF_TAIL
-        }
-        if constexpr ((T & 3) != 0) {   // restore Q0 = the next epoch's P_k
-#pragma unroll
-            for (int i = 0; i < RP; ++i) {
-                const f32x2 a0 = QW(1)[i], a1 = QW(2)[i], a2 = QW(3)[i], a3 = QW(4)[i];
-                Q0[i] = a0; Q1[i] = a1; Q2[i] = a2; Q3[i] = a3;
-            }
         }
     }
+    for (; e < nep; ++e) ADJR_EPOCH
+#undef ADJR_EPOCH
+#undef ADJR_EPOCH_STEPS
 #undef QW
 #undef DLOAD
 #undef ADJ_ISSUE
@@ -2797,6 +2829,7 @@ struct rdq_fwi_plan {
     int fwd_T = 4, adj_T = 4;   // time steps per launch (temporal blocking depth), <= TB_MAXT
     int fwd_delay = RDQ_SWEEP_DELAY_FWD, adj_delay = RDQ_SWEEP_DELAY_ADJ;   // persistent kernels' pre-sweep delay (ticks)
     int adj_ov = RDQ_OVERLAP_ADJ;   // the persistent (recurrence) adjoint's hand-off overlap mode
+    int adj_roles = 1;              // wave roles of the persistent (recurrence) adjoint (rdq_fwi_set_wave_roles)
     int adj_Tw = 0;             // the wide chunked adjoint's depth (<= TW_ADJ_MAXT); 0 = auto, see wide_adj_depth
     int fwd_Tw = 0;             // the wide chunked forward's depth (<= TW_FWD_MAXT); 0 = auto, see wide_fwd_depth
     int adj_spw = 0;            // the wide chunked adjoint's shots per workgroup, 0 = auto (wide_spw)
@@ -3141,6 +3174,9 @@ KernelRef<AdjPtArgs> adj_pt_T(int NW, int rw, bool fma)
 // The hand-off overlap mode the persistent adjoint runs (0 = the plain order): mode 1 is built at PT_OV_T
 // steps per epoch, for the recurrence adjoint.
 int adj_overlap(const rdq_fwi_plan *p) { return p->adj_T == PT_OV_T && p->adj_fma ? p->adj_ov : 0; }
+// The wave-role mode the persistent adjoint runs (0 = every wave the generic loop): the plain role is built
+// at PT_ROLES_T steps per epoch, in the recurrence adjoint.
+int adj_wave_roles(const rdq_fwi_plan *p) { return p->adj_T == PT_ROLES_T && p->adj_fma ? p->adj_roles : 0; }
 KernelRef<AdjPtArgs> adj_pt_kernel(const rdq_fwi_plan *p, int NW, int T, bool fma, bool prof)
 {
     static_assert(PT_OV_T == 4, "the profiled and the overlap builds share their depth");
@@ -3381,6 +3417,7 @@ int launch_adjoint_pt(rdq_fwi_plan *p, int B, int NW, int per, const float *coef
     a.status = p->d_status; a.nt = p->g.nt; a.nblk = nblk_alloc; a.prof = p->d_prof ? p->d_prof + PROF_WORDS : nullptr;
     a.xcd_mode = p->xcd_mode;
     a.sweep_delay = p->adj_delay;
+    a.roles = adj_wave_roles(p);
     for (int s0 = 0; s0 < B * p->g.ns; s0 += per) {
         a.g.sl_off = s0;
         a.g.nsl = std::min(per, B * p->g.ns - s0);
@@ -3860,7 +3897,7 @@ int rdq_fwi_set_persistent(rdq_fwi_plan *p, int32_t mode)
     return 0;
 }
 
-int rdq_fwi_launch_info(rdq_fwi_plan *p, int32_t B, int32_t out[8])
+int rdq_fwi_launch_info(rdq_fwi_plan *p, int32_t B, int32_t out[10])
 {
     if (!p || !out || B < 1) return RDQ_E_INVALID;
     std::lock_guard<std::mutex> lk(p->mu);
@@ -3876,6 +3913,8 @@ int rdq_fwi_launch_info(rdq_fwi_plan *p, int32_t B, int32_t out[8])
     out[5] = out[1] ? (ns + pera - 1) / pera : count_launches(chunked_schedule(p, B, Pass::adj_hist, all), Launch::adj);
     out[6] = 0;   // the forward has the one order
     out[7] = out[1] ? adj_overlap(p) : 0;
+    out[8] = 0;   // the forward has the generic loop only
+    out[9] = out[1] ? adj_wave_roles(p) : 0;
     return 0;
 }
 
@@ -3893,6 +3932,14 @@ int rdq_fwi_set_handoff_overlap(rdq_fwi_plan *p, int32_t fwd_mode, int32_t adj_m
     if (!p || fwd_mode != 0 || adj_mode < 0 || adj_mode > 1) return RDQ_E_INVALID;
     std::lock_guard<std::mutex> lk(p->mu);
     p->adj_ov = adj_mode;   // (persistent launches are direct, not graphs: nothing cached to drop)
+    return 0;
+}
+
+int rdq_fwi_set_wave_roles(rdq_fwi_plan *p, int32_t fwd_mode, int32_t adj_mode)
+{
+    if (!p || fwd_mode != 0 || adj_mode < 0 || adj_mode > 1) return RDQ_E_INVALID;
+    std::lock_guard<std::mutex> lk(p->mu);
+    set_knob(p, p->adj_roles, adj_mode);   // (drops the cached graphs when the value changes)
     return 0;
 }
 

@@ -158,14 +158,16 @@ class FwiPlan:
     def launch_info(self, B):
         """{'fwd_persistent', 'adj_persistent', 'fwd_class' / 'adj_class' (persistent region class: 16 /
         12 / 8, 0 = chunked), 'fwd_T', 'adj_T', 'fwd_launches', 'adj_launches', 'fwd_overlap' /
-        'adj_overlap' (the hand-off overlap mode that runs, set_handoff_overlap)} of a
+        'adj_overlap' (the hand-off overlap mode that runs, set_handoff_overlap), 'fwd_roles' /
+        'adj_roles' (the wave-role mode that runs, set_wave_roles)} of a
         call with batch B (launches: time-loop kernel launches per call)."""
-        out = (ctypes.c_int32 * 8)()
+        out = (ctypes.c_int32 * 10)()
         _hip.check(self.lib.rdq_fwi_launch_info(self.handle, int(B), out), "rdq_fwi_launch_info")
         return {"fwd_persistent": bool(out[0]), "adj_persistent": bool(out[1]),
                 "fwd_class": int(out[0]), "adj_class": int(out[1]), "fwd_T": int(out[2]),
                 "adj_T": int(out[3]), "fwd_launches": int(out[4]), "adj_launches": int(out[5]),
-                "fwd_overlap": int(out[6]), "adj_overlap": int(out[7])}
+                "fwd_overlap": int(out[6]), "adj_overlap": int(out[7]),
+                "fwd_roles": int(out[8]), "adj_roles": int(out[9])}
 
     def set_sweep_delay(self, fwd_ticks, adj_ticks):
         """Persistent kernels: 10 ns ticks between an epoch's publish and its first hand-off pass."""
@@ -178,6 +180,13 @@ class FwiPlan:
         are bit-identical in both modes."""
         _hip.check(self.lib.rdq_fwi_set_handoff_overlap(self.handle, int(fwd_mode), int(adj_mode)),
                    "rdq_fwi_set_handoff_overlap")
+
+    def set_wave_roles(self, fwd_mode, adj_mode):
+        """Persistent kernels: adjoint 1 (default) = waves without the source or the receiver row run every
+        epoch but the last in a loop without the per-step source / receiver / end-of-record tests; 0 = every
+        wave runs the generic loop.  The forward has mode 0 only.  Results are bit-identical in both modes."""
+        _hip.check(self.lib.rdq_fwi_set_wave_roles(self.handle, int(fwd_mode), int(adj_mode)),
+                   "rdq_fwi_set_wave_roles")
 
     def wide_info(self, B):
         """{'chains', 'fwd_spw', 'adj_spw', 'chain0_shots'}: the wide chunked kernels' concurrent launch

@@ -5,7 +5,8 @@ split wait_a_issue / wait_b_first / wait_c_later / wait_d_tail, publish_issue an
 --overlap F,A sets the hand-off overlap modes; --ab N times the mode pairs of --ab-modes (default "0,0;0,1":
 the first is the baseline) alternated N times each, event-timed per kernel: one JSON line per run and a
 summary line with the bar a mode has to pass (every run faster than every baseline run, and the medians
-apart by at least three times the larger min-max spread)."""
+apart by at least three times the larger min-max spread).  --roles F,A sets the wave-role modes;
+--ab-knob roles makes --ab alternate wave-role mode pairs instead (e.g. --ab-modes "0,0;1,1")."""
 import argparse
 import json
 import os
@@ -33,6 +34,8 @@ ap.add_argument("--delay", default=None, help="pre-sweep delays of the persisten
 ap.add_argument("--overlap", default=None, help="hand-off overlap modes of the persistent kernels, 'fwd,adj'")
 ap.add_argument("--ab", type=int, default=0, help="rounds of an alternated A/B of hand-off overlap modes")
 ap.add_argument("--ab-modes", default="0,0;0,1", help="'fwd,adj' mode pairs of the A/B, baseline first")
+ap.add_argument("--ab-knob", default="overlap", choices=["overlap", "roles"], help="the setting --ab alternates")
+ap.add_argument("--roles", default=None, help="wave-role modes of the persistent kernels, 'fwd,adj'")
 a = ap.parse_args()
 dev = torch.device("cuda:0")
 ctx = dict(n_grid=70, nt=a.nt, dx=10.0, dt=0.001, nbc=120, f=15.0, sz=10, gz=10, ng=70, ns=a.ns)
@@ -45,6 +48,8 @@ if a.delay:
     plan.set_sweep_delay(*[int(x) for x in a.delay.split(",")])
 if a.overlap:
     plan.set_handoff_overlap(*[int(x) for x in a.overlap.split(",")])
+if a.roles:
+    plan.set_wave_roles(*[int(x) for x in a.roles.split(",")])
 sz = plan.sizes(a.B)
 dseis = torch.randn(a.B, a.ns, sz.nrec, plan.ng, device=dev)
 
@@ -77,12 +82,12 @@ if a.ab:
     timed(a.reps)                                         # warm-up (clocks, allocator), not recorded
     for rnd in range(a.ab):
         for m in pairs:
-            plan.set_handoff_overlap(*m)
+            (plan.set_wave_roles if a.ab_knob == "roles" else plan.set_handoff_overlap)(*m)
             info = plan.launch_info(a.B)
-            assert (info["fwd_overlap"], info["adj_overlap"]) == m, info
+            assert (info[f"fwd_{a.ab_knob}"], info[f"adj_{a.ab_knob}"]) == m, info
             fw, ad = timed(a.reps)
             runs[m].append((fw, ad))
-            print(json.dumps({"round": rnd, "overlap": list(m), "fwd_ms": round(fw, 4), "adj_ms": round(ad, 4)}),
+            print(json.dumps({"round": rnd, a.ab_knob: list(m), "fwd_ms": round(fw, 4), "adj_ms": round(ad, 4)}),
                   flush=True)
     summ = {}
     for k, name in ((0, "fwd"), (1, "adj")):
@@ -97,7 +102,7 @@ if a.ab:
                 "base_ms": [round(x, 4) for x in base], "new_ms": [round(x, 4) for x in new],
                 "median_gain_ms": round(gain, 4), "max_spread_ms": round(spread, 4),
                 "every_new_beats_every_base": new[-1] < base[0], "gain_over_3_spreads": gain >= 3 * spread}
-    print(json.dumps({"ab_summary": summ, "ns": a.ns, "nt": a.nt, "reps": a.reps}), flush=True)
+    print(json.dumps({"ab_summary": summ, "knob": a.ab_knob, "ns": a.ns, "nt": a.nt, "reps": a.reps}), flush=True)
     sys.exit(0)
 
 res = []
@@ -126,6 +131,7 @@ for T, G in cfgs:
     fw, ad = sorted(fw)[len(fw) // 2], sorted(ad)[len(ad) // 2]
     res.append({"T": T, "persistent": G, "mode": a.mode, "rw": a.rw, "delay": a.delay, "ns": a.ns,
                 "overlap": [plan.launch_info(a.B)["fwd_overlap"], plan.launch_info(a.B)["adj_overlap"]],
+                "roles": [plan.launch_info(a.B).get("fwd_roles", 0), plan.launch_info(a.B).get("adj_roles", 0)],
                 "fwd_launches": plan.launch_info(a.B)["fwd_launches"], "fwd_ms": round(fw, 3), "adj_ms": round(ad, 3),
                 "shot_ts_per_s": round(a.ns * a.nt * a.B / ((fw + ad) * 1e-3))})
     if a.profile and G:
