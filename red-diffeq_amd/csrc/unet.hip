@@ -11,6 +11,7 @@
 //   group_norm    fp64 per-(sample, group) statistics from per-chunk partials, then normalise +
 //                 time-conditioned scale/shift + SiLU in one pass.
 //   rmsnorm / linear / sinusoidal embedding / linear & full attention / RED prologue-epilogue.
+//   sample_step   the fused reverse step of p_sample / ddim_sample (red_diffeq_sampling.h).
 #include <hip/hip_runtime.h>
 #include <atomic>
 
@@ -21,6 +22,7 @@
 #include <type_traits>
 
 #include "red_diffeq_unet.h"
+#include "red_diffeq_sampling.h"
 
 namespace {
 
@@ -2229,6 +2231,128 @@ __global__ __launch_bounds__(256) void k_red_epilogue(int64_t n, const float *__
     g[o] = pn - eps[o];
 }
 
+// ------------------------------------------------------------------ prior sampling: reverse step
+// One launch per reverse step of p_sample / ddim_sample (reference diffusion.py:411-446, 469-494);
+// contract in red_diffeq_sampling.h.  Memory-bound: 3 reads + 1..2 writes per element, 16 bytes per
+// lane where the layout allows.  The schedule entries of the sample's timestep are uniform over the
+// workgroup (blockIdx.y = sample) and read once, ahead of the element loop.
+struct SampleStepArgs {
+    int64_t n;
+    int32_t objective, mode, T;
+    rdq_sample_tables tab;
+    const int64_t *t;
+    const float *x, *out, *noise;      // x is NOT restrict: x_next may alias it
+    float a_next, c, sigma;
+    int64_t t_next;
+    float *x_next, *x_start_out;
+    int64_t *t_out;
+};
+
+struct SampleStepCoef {
+    float sr, srm1, sa, s1ma, c1, c2, sd;
+};
+
+// One element.  Each product the reference rounds on its own is a named float, and contraction is off
+// inside this function, so the result is the reference's fp32 expression tree.
+__device__ __forceinline__ float sample_step_elem(const SampleStepArgs &a, const SampleStepCoef &k, float x, float o,
+                                                  float z, bool has_noise, float *x0_out)
+{
+#pragma clang fp contract(off)
+    const float u = k.sr * x;                          // sr[t] * x_t (394, 397)
+    float x0;
+    if (a.objective == RDQ_OBJ_PRED_NOISE) {
+        const float w = k.srm1 * o;
+        x0 = u - w;                                    // predict_start_from_noise (394)
+    } else if (a.objective == RDQ_OBJ_PRED_X0) {
+        x0 = o;                                        // (421)
+    } else {
+        const float p = k.sa * x;
+        const float q = k.s1ma * o;
+        x0 = p - q;                                    // predict_start_from_v (403)
+    }
+    x0 = fminf(fmaxf(x0, -1.0f), 1.0f);                // maybe_clip (417/422/427), clamp_ (435)
+    *x0_out = x0;
+    if (a.mode == RDQ_STEP_DDIM_LAST) return x0;       // time_next < 0 (481-483)
+    if (a.mode == RDQ_STEP_ANCESTRAL) {
+        const float m1 = k.c1 * x0;
+        const float m2 = k.c2 * x;
+        const float mean = m1 + m2;                    // q_posterior (406)
+        if (!has_noise) return mean;                   // t == 0: noise = 0.0 (444)
+        const float nz = k.sd * z;                     // (0.5 * logvar).exp() * noise (445)
+        return mean + nz;
+    }
+    const float d = u - x0;
+    const float eps = d / k.srm1;                      // predict_noise_from_start (397)
+    const float p1 = x0 * a.a_next;                    // x_start * alpha_next.sqrt() (490)
+    const float p2 = a.c * eps;                        // c * pred_noise
+    const float s = p1 + p2;
+    if (!has_noise) return s;                          // sigma == 0
+    const float p3 = a.sigma * z;                      // sigma * noise
+    return s + p3;
+}
+
+template <bool VEC>
+__global__ __launch_bounds__(256) void k_sample_step(SampleStepArgs a)
+{
+    const int b = blockIdx.y;
+    int64_t tb = a.t[b];
+    tb = tb < 0 ? 0 : (tb >= a.T ? (int64_t)a.T - 1 : tb);           // never index outside the tables
+    const bool has_noise = a.noise != nullptr && a.mode != RDQ_STEP_DDIM_LAST;
+    const bool ddim = a.mode == RDQ_STEP_DDIM;
+    SampleStepCoef k = {0.0f, 1.0f, 0.0f, 0.0f, 0.0f, 0.0f, 0.0f};
+    if (a.objective == RDQ_OBJ_PRED_NOISE || ddim) {
+        k.sr = a.tab.sqrt_recip_ac[tb];
+        k.srm1 = a.tab.sqrt_recipm1_ac[tb];
+    }
+    if (a.objective == RDQ_OBJ_PRED_V) {
+        k.sa = a.tab.sqrt_ac[tb];
+        k.s1ma = a.tab.sqrt_1mac[tb];
+    }
+    if (a.mode == RDQ_STEP_ANCESTRAL) {
+        k.c1 = a.tab.post_coef1[tb];
+        k.c2 = a.tab.post_coef2[tb];
+        if (has_noise) {
+            const float hl = 0.5f * a.tab.post_logvar[tb];
+            k.sd = expf(hl);
+        }
+    }
+    if (a.t_out && a.t_next >= 0 && blockIdx.x == 0 && threadIdx.x == 0) a.t_out[b] = a.t_next;
+
+    const size_t base = (size_t)b * a.n;
+    const int64_t stride = (int64_t)gridDim.x * blockDim.x;
+    const int64_t first = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (VEC) {
+        const int64_t n4 = a.n >> 2;                   // host: n % 4 == 0, all pointers 16-byte aligned
+        const f32x4 *xv = reinterpret_cast<const f32x4 *>(a.x + base);
+        const f32x4 *ov = reinterpret_cast<const f32x4 *>(a.out + base);
+        const f32x4 *zv = has_noise ? reinterpret_cast<const f32x4 *>(a.noise + base) : nullptr;
+        f32x4 *yv = reinterpret_cast<f32x4 *>(a.x_next + base);
+        f32x4 *sv = a.x_start_out ? reinterpret_cast<f32x4 *>(a.x_start_out + base) : nullptr;
+        for (int64_t i = first; i < n4; i += stride) {
+            const f32x4 x = xv[i], o = ov[i];
+            const f32x4 z = has_noise ? zv[i] : f32x4{0.0f, 0.0f, 0.0f, 0.0f};
+            f32x4 y, x0;
+#pragma unroll
+            for (int j = 0; j < 4; ++j) {
+                float x0j;
+                y[j] = sample_step_elem(a, k, x[j], o[j], z[j], has_noise, &x0j);
+                x0[j] = x0j;
+            }
+            yv[i] = y;
+            if (sv) sv[i] = x0;
+        }
+    } else {
+        for (int64_t i = first; i < a.n; i += stride) {
+            const float x = a.x[base + i], o = a.out[base + i];
+            const float z = has_noise ? a.noise[base + i] : 0.0f;
+            float x0;
+            const float y = sample_step_elem(a, k, x, o, z, has_noise, &x0);
+            a.x_next[base + i] = y;
+            if (a.x_start_out) a.x_start_out[base + i] = x0;
+        }
+    }
+}
+
 template <int KH>
 void launch_conv_ig(dim3 grid, hipStream_t st, const IgArgs &a)
 {
@@ -4413,6 +4537,35 @@ int rdq_red_epilogue(int32_t B, int64_t n, const float *sr, const float *srm1, c
     if (B < 1 || n < 1 || !sr || !srm1 || !t || !xt || !eh || !eps || !g) return RDQ_E_INVALID;
     hipLaunchKernelGGL(k_red_epilogue, dim3((unsigned)((n + 255) / 256), B), dim3(256), 0, st, n, sr, srm1, t, xt, eh,
                        eps, g);
+    RDQ_CHECK(hipGetLastError());
+    return 0;
+}
+
+int rdq_sample_step(int32_t B, int64_t n, int32_t objective, int32_t mode, int32_t T, const rdq_sample_tables *tab,
+                    const int64_t *t, const float *x_t, const float *out, const float *noise, float a_next, float c,
+                    float sigma, int64_t t_next, float *x_next, float *x_start_out, int64_t *t_out, hipStream_t st)
+{
+    if (B < 1 || B > 65535 || n < 1 || T < 1 || !tab || !t || !x_t || !out || !x_next) return RDQ_E_INVALID;
+    if (objective < RDQ_OBJ_PRED_NOISE || objective > RDQ_OBJ_PRED_V) return RDQ_E_INVALID;
+    if (mode < RDQ_STEP_ANCESTRAL || mode > RDQ_STEP_DDIM_LAST) return RDQ_E_INVALID;
+    if ((objective == RDQ_OBJ_PRED_NOISE || mode == RDQ_STEP_DDIM) && (!tab->sqrt_recip_ac || !tab->sqrt_recipm1_ac))
+        return RDQ_E_INVALID;
+    if (objective == RDQ_OBJ_PRED_V && (!tab->sqrt_ac || !tab->sqrt_1mac)) return RDQ_E_INVALID;
+    if (mode == RDQ_STEP_ANCESTRAL && (!tab->post_coef1 || !tab->post_coef2 || (noise && !tab->post_logvar)))
+        return RDQ_E_INVALID;
+    if (mode == RDQ_STEP_DDIM && !noise && sigma != 0.0f) return RDQ_E_INVALID;
+    if (t_next >= T || (const void *)t_out == (const void *)t || x_start_out == x_t || x_start_out == x_next)
+        return RDQ_E_INVALID;
+    SampleStepArgs a;
+    a.n = n; a.objective = objective; a.mode = mode; a.T = T; a.tab = *tab; a.t = t;
+    a.x = x_t; a.out = out; a.noise = noise; a.a_next = a_next; a.c = c; a.sigma = sigma; a.t_next = t_next;
+    a.x_next = x_next; a.x_start_out = x_start_out; a.t_out = t_out;
+    auto al16 = [](const void *p) { return (reinterpret_cast<uintptr_t>(p) & 15) == 0; };
+    const bool vec = n % 4 == 0 && al16(x_t) && al16(out) && al16(noise) && al16(x_next) && al16(x_start_out);
+    const int64_t items = vec ? n / 4 : n;
+    const dim3 grid((unsigned)std::min<int64_t>((items + 255) / 256, 1024), B);
+    if (vec) hipLaunchKernelGGL(k_sample_step<true>, grid, dim3(256), 0, st, a);
+    else hipLaunchKernelGGL(k_sample_step<false>, grid, dim3(256), 0, st, a);
     RDQ_CHECK(hipGetLastError());
     return 0;
 }

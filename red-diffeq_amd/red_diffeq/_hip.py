@@ -44,6 +44,12 @@ class ConvDesc(ctypes.Structure):
     _fields_ = [(n, c_int32) for n in ("B", "cin1", "cin2", "H", "W", "cout", "kh", "kw", "pad", "in_mode")]
 
 
+class SampleTables(ctypes.Structure):
+    """struct rdq_sample_tables."""
+    _fields_ = [(n, c_void_p) for n in ("sqrt_recip_ac", "sqrt_recipm1_ac", "sqrt_ac", "sqrt_1mac", "post_coef1",
+                                        "post_coef2", "post_logvar")]
+
+
 # name -> (restype, argtypes); must match include/*.h (tests check every symbol)
 SIGNATURES = {
     "rdq_fwi_plan_create": (c_int32, [ctypes.POINTER(FwiGeom), ctypes.POINTER(c_void_p)]),
@@ -170,6 +176,10 @@ SIGNATURES = {
                                      c_void_p, c_void_p]),
     "rdq_red_epilogue": (c_int32, [c_int32, c_int64, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p,
                                    c_void_p, c_void_p]),
+    # include/red_diffeq_sampling.h
+    "rdq_sample_step": (c_int32, [c_int32, c_int64, c_int32, c_int32, c_int32, ctypes.POINTER(SampleTables), c_void_p,
+                                  c_void_p, c_void_p, c_void_p, c_float, c_float, c_float, c_int64, c_void_p, c_void_p,
+                                  c_void_p, c_void_p]),
     # include/red_diffeq_loop.h
     "rdq_adam_step": (c_int32, [c_int64, c_void_p, c_void_p, c_void_p, c_void_p, c_float, c_float, c_float, c_float,
                                 c_float, c_int32, c_float, c_float, c_void_p, c_void_p]),

@@ -1,12 +1,13 @@
 """U-Net epsilon-predictor and Gaussian diffusion schedule — inference subset of the reference
 red_diffeq/models/diffusion.py (Unet 220-301, blocks 78-218, schedules 304-326,
-GaussianDiffusion 328-437, q_sample 516-519).
+GaussianDiffusion 328-437, prior sampling 439-514, q_sample 516-519).
 
 Module tree and parameter names are the reference's, so a reference checkpoint
 (``torch.load(path)["model"]`` = a GaussianDiffusion state_dict, 296 keys at dim=64) loads
 unchanged.  The RED regulariser only runs the forward pass (its U-Net output is detached,
-regularization/diffusion.py:74), so training/sampling loops (p_losses, Trainer, Dataset,
-ddim/p_sample loops) are out of scope.
+regularization/diffusion.py:74).  Drawing from the prior (p_sample, p_sample_loop, ddim_sample,
+sample, interpolate) is built on the same forward: one captured-graph replay and one fused reverse-step
+launch per step.  Training (p_losses, Trainer, Dataset) is out of scope.
 
 The arithmetic of every block goes through ``red_diffeq.models.unet_ops``.
 """
@@ -410,7 +411,10 @@ def sigmoid_beta_schedule(timesteps, start=-3, end=3, tau=1, clamp_min=1e-05):
 
 
 class GaussianDiffusion(nn.Module):
-    """Schedule buffers + the inference-side q/p math (reference diffusion.py:328-437, 516-519)."""
+    """Schedule buffers, the inference-side q/p math (reference diffusion.py:328-437, 516-519) and the prior
+    samplers (439-514): sample() / p_sample_loop() / ddim_sample() / p_sample() / interpolate() with the
+    reference's names, arguments, return values and draw order, plus keyword-only ``generator=`` (a torch
+    Generator) and ``noise=`` (pre-drawn tensors consumed in draw order).  No training side (p_losses)."""
 
     def __init__(self, model, *, image_size, timesteps=1000, sampling_timesteps=None, objective="pred_v",
                  beta_schedule="sigmoid", schedule_fn_kwargs=dict(), ddim_sampling_eta=0.0,
@@ -526,3 +530,166 @@ class GaussianDiffusion(nn.Module):
         noise = default(noise, lambda: torch.randn_like(x_start))
         return extract(self.sqrt_alphas_cumprod, t, x_start.shape) * x_start + \
             extract(self.sqrt_one_minus_alphas_cumprod, t, x_start.shape) * noise
+
+    # ------------------------------------------------------------------ prior sampling (reference 439-514)
+    # Every reverse step is ONE fused launch (ops.sample_step -> rdq_sample_step).  The methods run under
+    # torch.no_grad() where the reference uses inference_mode: the captured forward's static buffers are shared
+    # with the RED regulariser, which writes them outside inference mode.
+    def _drawer(self, noise, generator):
+        """draw(shape, device) -> the next standard-normal tensor, in the reference's draw order: from `noise`
+        (a tensor or an iterable of pre-drawn tensors) when given, else torch.randn (on `generator`)."""
+        if noise is not None:
+            it = iter([noise] if torch.is_tensor(noise) else noise)
+
+            def draw(shape, device):
+                z = next(it)
+                if tuple(z.shape) != tuple(shape):
+                    raise ValueError(f"noise= draw of shape {tuple(z.shape)}, the sampler needs {tuple(shape)}")
+                return z.to(device=device, dtype=torch.float32).contiguous()
+            return draw
+
+        def draw(shape, device):
+            if generator is not None and generator.device.type != torch.device(device).type:
+                return torch.randn(shape, generator=generator, dtype=torch.float32).to(device)
+            return torch.randn(shape, device=device, generator=generator, dtype=torch.float32)
+        return draw
+
+    def _step_times(self, times, B, device):
+        """int64 [len(times), B] on the device, row i = the timestep of step i for every sample: what the step
+        kernel reads as t while it writes the next t into the forward's static input.  Uploaded once per
+        (times, B, device) and kept, so a repeated sampling call does not touch the host again."""
+        cache = self.__dict__.setdefault("_step_times_cache", {})
+        key = (times, B, torch.device(device))
+        if key not in cache:
+            if len(cache) >= 8:
+                cache.clear()
+            cache[key] = torch.tensor(times, dtype=torch.long)[:, None].expand(-1, B).contiguous().to(device)
+        return cache[key]
+
+    def _reverse_steps(self, img, steps, draw, keep=None):
+        """Run `steps` = [(t, t_next, ddim, stochastic)] from img; returns (img, last x_start or None).
+        ddim: None (ancestral), (sqrt(alpha_next), c, sigma) or "last"; keep: a list that receives every
+        step's image.  Where the U-Net replays a captured forward, a step is one replay, one step launch
+        writing x_next and the next t into the forward's static inputs, and at most one randn; otherwise
+        self.model(x, t, self_cond) with the same step kernel.  Nothing here reads a device value."""
+        if not steps:
+            return img, None
+        shape, device, B = tuple(img.shape), img.device, img.shape[0]
+        tables = ops.sample_tables(self)
+        tt = self._step_times(tuple(s[0] for s in steps), B, device)
+        io = self.model.graph_io(shape, device) if img.dim() == 4 else None
+        if io is not None:
+            xs, ts = io
+            xs.copy_(img)
+            ts.copy_(tt[0])
+            for i, (t, t_next, ddim, stochastic) in enumerate(steps):
+                out = self.model.replay_static(xs, ts)
+                z = draw(shape, device) if stochastic else None
+                ops.sample_step(self, xs, tt[i], out, z, xs, ddim=ddim, t_next=t_next, t_out=ts, tables=tables)
+                if keep is not None:
+                    keep.append(xs.clone())
+            return xs.clone(), None
+        x = img.to(torch.float32).contiguous()
+        x_start = None
+        for i, (t, t_next, ddim, stochastic) in enumerate(steps):
+            out = self.model(x, tt[i], x_start if self.self_condition else None)
+            z = draw(shape, device) if stochastic else None
+            x_start = torch.empty_like(x) if self.self_condition else None
+            x = ops.sample_step(self, x, tt[i], out.contiguous(), z, torch.empty_like(x), ddim=ddim, t_next=t_next,
+                                x_start_out=x_start, tables=tables)
+            if keep is not None:
+                keep.append(x)
+        return x, x_start
+
+    @torch.no_grad()
+    def p_sample(self, x, t: int, x_self_cond=None, *, generator=None, noise=None):
+        """One ancestral step (reference 439-446): (pred_img, x_start); one draw unless t == 0."""
+        x = x.to(torch.float32).contiguous()
+        bt = torch.full((x.shape[0],), t, device=x.device, dtype=torch.long)
+        out = self.model(x, bt, x_self_cond)
+        z = self._drawer(noise, generator)(tuple(x.shape), x.device) if t > 0 else None
+        x_start = torch.empty_like(x)
+        pred = ops.sample_step(self, x, bt, out.contiguous(), z, torch.empty_like(x), x_start_out=x_start)
+        return pred, x_start
+
+    @torch.no_grad()
+    def p_sample_loop(self, shape, return_all_timesteps=False, plot_show=False, *, generator=None, noise=None):
+        """Ancestral sampling over all num_timesteps (reference 454-466).  plot_show is accepted and ignored."""
+        draw = self._drawer(noise, generator)
+        img = draw(tuple(shape), self.device)
+        imgs = [img]
+        steps = [(t, t - 1, None, t > 0) for t in reversed(range(self.num_timesteps))]
+        img, _ = self._reverse_steps(img, steps, draw, imgs if return_all_timesteps else None)
+        ret = img if not return_all_timesteps else torch.stack(imgs, dim=1)
+        return self.unnormalize(ret)
+
+    def _ddim_schedule(self):
+        """ddim_schedule of this object's tables; the CPU copy of alphas_cumprod is fetched when the buffer, the
+        step count or eta changed, never per step."""
+        ac = self.alphas_cumprod
+        key = (ac.data_ptr(), ac._version, ac.device, self.num_timesteps, self.sampling_timesteps,
+               self.ddim_sampling_eta)
+        hit = self.__dict__.get("_ddim_cache")
+        if hit is None or hit[0] != key:
+            hit = (key, ddim_schedule(ac.detach().cpu(), self.num_timesteps, self.sampling_timesteps,
+                                      self.ddim_sampling_eta))
+            self.__dict__["_ddim_cache"] = hit
+        return hit[1]
+
+    @torch.no_grad()
+    def ddim_sample(self, shape, return_all_timesteps=False, *, generator=None, noise=None):
+        """DDIM sampling over sampling_timesteps (reference 468-494, clip_x_start, rederive_pred_noise): one draw
+        per step except the last (time_next < 0), also when eta = 0, as the reference."""
+        pairs, coef = self._ddim_schedule()
+        draw = self._drawer(noise, generator)
+        img = draw(tuple(shape), self.device)
+        imgs = [img]
+        steps = [(t, tn, "last", False) if tn < 0 else (t, tn, tuple(k), True)
+                 for (t, tn), k in zip(pairs, coef.tolist())]
+        img, _ = self._reverse_steps(img, steps, draw, imgs if return_all_timesteps else None)
+        ret = img if not return_all_timesteps else torch.stack(imgs, dim=1)
+        return self.unnormalize(ret)
+
+    @torch.no_grad()
+    def sample(self, batch_size=16, return_all_timesteps=False, *, generator=None, noise=None):
+        """Draw from the prior (reference 496-500): DDIM when sampling_timesteps < num_timesteps, else ancestral.
+        (batch, channels, H, W) in [0, 1] after unnormalize; with return_all_timesteps the steps stack on dim 1."""
+        (h, w), channels = self.image_size, self.channels
+        fn = self.p_sample_loop if not self.is_ddim_sampling else self.ddim_sample
+        return fn((batch_size, channels, h, w), return_all_timesteps=return_all_timesteps, generator=generator,
+                  noise=noise)
+
+    @torch.no_grad()
+    def interpolate(self, x1, x2, t=None, lam=0.5, *, generator=None, noise=None):
+        """Noise x1 and x2 to step t, mix, and denoise ancestrally from t - 1 (reference 502-514); draws: one
+        per q_sample (x1 then x2), then one per step above 0."""
+        b, device = x1.shape[0], x1.device
+        t = default(t, self.num_timesteps - 1)
+        assert x1.shape == x2.shape
+        draw = self._drawer(noise, generator)
+        tb = torch.full((b,), t, device=device)
+        xt1, xt2 = (self.q_sample(x, t=tb, noise=draw(tuple(x.shape), device)) for x in (x1, x2))
+        img = (1 - lam) * xt1 + lam * xt2
+        steps = [(i, i - 1, None, i > 0) for i in reversed(range(t))]
+        img, _ = self._reverse_steps(img, steps, draw)
+        return img
+
+
+def ddim_schedule(alphas_cumprod_cpu, num_timesteps, sampling_timesteps, eta):
+    """The host side of ddim_sample (reference 471-473, 485-488), in the reference's fp32 torch expressions
+    on a CPU copy of alphas_cumprod: (pairs, coef) with pairs = [(time, time_next)] and coef a float32
+    [S, 3] tensor of (sqrt(alpha_next), c, sigma) per step; the row of the last step (time_next < 0) is zero."""
+    ac = alphas_cumprod_cpu
+    times = torch.linspace(-1, num_timesteps - 1, steps=sampling_timesteps + 1)
+    times = list(reversed(times.int().tolist()))
+    pairs = list(zip(times[:-1], times[1:]))
+    coef = torch.zeros(len(pairs), 3, dtype=torch.float32)
+    for i, (time, time_next) in enumerate(pairs):
+        if time_next < 0:
+            continue
+        alpha = ac[time]
+        alpha_next = ac[time_next]
+        sigma = eta * ((1 - alpha / alpha_next) * (1 - alpha_next) / (1 - alpha)).sqrt()
+        c = (1 - alpha_next - sigma ** 2).sqrt()
+        coef[i, 0], coef[i, 1], coef[i, 2] = alpha_next.sqrt(), c, sigma
+    return pairs, coef

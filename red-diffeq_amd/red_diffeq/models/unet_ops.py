@@ -262,6 +262,31 @@ def red_epilogue(diff, xt, t, eps_hat, eps):
                                         diff.sqrt_recipm1_alphas_cumprod)
 
 
+def sample_tables(diff):
+    """The seven schedule buffers of a GaussianDiffusion in the order ops.sample_step takes them."""
+    return [diff.sqrt_recip_alphas_cumprod, diff.sqrt_recipm1_alphas_cumprod, diff.sqrt_alphas_cumprod,
+            diff.sqrt_one_minus_alphas_cumprod, diff.posterior_mean_coef1, diff.posterior_mean_coef2,
+            diff.posterior_log_variance_clipped]
+
+
+def sample_step(diff, x_t, t, out, noise, x_next, *, ddim=None, t_next=-1, x_start_out=None, t_out=None,
+                tables=None):
+    """One fused reverse step (diffusion.py:411-446, 469-494) written into x_next (may be x_t).
+    ddim None: the ancestral step of p_sample (noise None at t = 0).  ddim = (sqrt(alpha_next), c, sigma) as
+    Python floats: the DDIM step; ddim = "last": the closing DDIM step (time_next < 0), x_next = x0."""
+    from ..ops import SAMPLE_ANCESTRAL, SAMPLE_DDIM, SAMPLE_DDIM_LAST, SAMPLE_OBJECTIVES
+    if ddim is None:
+        mode, (a, c, s) = SAMPLE_ANCESTRAL, (0.0, 0.0, 0.0)
+    elif isinstance(ddim, str):
+        mode, (a, c, s) = SAMPLE_DDIM_LAST, (0.0, 0.0, 0.0)
+    else:
+        mode, (a, c, s) = SAMPLE_DDIM, ddim
+    torch.ops.red_diffeq.sample_step(x_t, t, out, noise, tables if tables is not None else sample_tables(diff),
+                                     SAMPLE_OBJECTIVES[diff.objective], mode, a, c, s, int(t_next), x_next,
+                                     x_start_out, t_out)
+    return x_next
+
+
 HIP_OPS = {"head", "first_block_and_scale_shifts", "last_block_and_out", "conv2d", "conv_group_norm_silu", "conv_group_norm_silu_shortcut", "block_pair", "linear", "time_mlp", "resnet_scale_shifts", "sinusoidal", "group_norm_affine_silu", "rmsnorm", "linear_attention",
-           "full_attention", "red_q_sample", "red_q_sample_into", "red_epilogue"}
+           "full_attention", "red_q_sample", "red_q_sample_into", "red_epilogue", "sample_step"}
 del math

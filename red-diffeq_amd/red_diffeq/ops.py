@@ -23,7 +23,9 @@ torch.compile see them as ordinary operators instead of opaque ctypes calls.
     conv2d_mfma, conv2d_rms, conv2d_gn_silu, conv2d_bf16_gn_silu, conv2d_bf16_gn_silu_out, conv2d_gn_silu_sc, conv2d_gn_silu_lsm, conv2d_gn_silu_out, unet_head,
     gn_silu, rmsnorm, linear, time_mlp, linear_silu_multi, sinusoidal_emb, linear_attn, linear_attn_block, attn,
     red_q_sample, red_q_sample_into, red_eps
-  loop (include/red_diffeq_loop.h)
+  prior sampling (include/red_diffeq_sampling.h)
+    sample_step(x_t, t, out, noise, tables, ...) writes x_next (and x_start_out / t_out): the fused reverse step
+  loop(include/red_diffeq_loop.h)
     l1_misfit / l1_misfit_backward, smooth_reg / smooth_reg_backward, metrics, adam_clamp_
 
 No CPU implementation is registered: a CPU tensor reaching an op raises (no fallback).
@@ -1060,6 +1062,51 @@ def red_eps(xt: Tensor, t: Tensor, eps_hat: Tensor, eps: Tensor, sqrt_recip_ac: 
 @red_eps.register_fake
 def _(xt, t, eps_hat, eps, sqrt_recip_ac, sqrt_recipm1_ac):
     return torch.empty_like(xt)
+
+
+SAMPLE_OBJECTIVES = {"pred_noise": 0, "pred_x0": 1, "pred_v": 2}       # RDQ_OBJ_*
+SAMPLE_ANCESTRAL, SAMPLE_DDIM, SAMPLE_DDIM_LAST = 0, 1, 2              # RDQ_STEP_*
+
+
+@torch.library.custom_op(f"{LIB}::sample_step", mutates_args=("x_next", "x_start_out", "t_out"))
+def sample_step(x_t: Tensor, t: Tensor, out: Tensor, noise: Optional[Tensor], tables: List[Tensor], objective: int,
+                step: int, a_next: float, c: float, sigma: float, t_next: int, x_next: Tensor,
+                x_start_out: Optional[Tensor], t_out: Optional[Tensor]) -> None:
+    """One reverse step of p_sample / ddim_sample (diffusion.py:411-446, 469-494; include/red_diffeq_sampling.h)
+    written into x_next (contiguous, x_t's shape; may be x_t itself).  t int64 [B]; tables = the seven fp32
+    schedule buffers (sqrt_recip_ac, sqrt_recipm1_ac, sqrt_ac, sqrt_1mac, posterior_mean_coef1, posterior_mean_coef2,
+    posterior_log_variance_clipped), all of one length; step = SAMPLE_ANCESTRAL / _DDIM / _DDIM_LAST.  noise None: the ancestral t = 0 step, or DDIM with
+    sigma == 0.  x_start_out (x_t's shape) receives the clamped x0, t_out (int64 [B]) t_next when t_next >= 0."""
+    _hip.require_device(x_t, t, out, noise, x_next, x_start_out, t_out, *tables)
+    B = x_t.shape[0]
+    if x_t.dtype != torch.float32 or not x_t.is_contiguous() or x_t.dim() < 1 or x_t.numel() == 0:
+        raise ValueError("sample_step: x_t must be a contiguous, non-empty fp32 tensor")
+    for name, v in (("out", out), ("noise", noise), ("x_next", x_next), ("x_start_out", x_start_out)):
+        if v is not None and (v.shape != x_t.shape or v.dtype != torch.float32 or not v.is_contiguous()):
+            raise ValueError(f"sample_step: {name} does not match x_t (shape, fp32, contiguous)")
+    for name, v in (("t", t), ("t_out", t_out)):
+        if v is not None and (v.dtype != torch.int64 or v.shape != (B,) or not v.is_contiguous()):
+            raise ValueError(f"sample_step: {name} must be a contiguous int64 [B]")
+    if t_out is not None and t_out.data_ptr() == t.data_ptr():
+        raise ValueError("sample_step: t_out must not be t")
+    if len(tables) != 7 or any(v.dtype != torch.float32 or v.dim() != 1 or v.shape != tables[0].shape
+                               or not v.is_contiguous() for v in tables):
+        raise ValueError("sample_step: tables must be seven contiguous fp32 vectors of one length")
+    T = tables[0].shape[0]
+    if objective not in (0, 1, 2) or step not in (0, 1, 2) or T < 1 or t_next >= T:
+        raise ValueError("sample_step: bad objective / step / t_next")
+    if step == SAMPLE_DDIM and noise is None and sigma != 0.0:
+        raise ValueError("sample_step: DDIM with sigma != 0 needs noise")
+    tab = _hip.SampleTables(*(t_.data_ptr() for t_ in tables))
+    _hip.check(_hip.lib().rdq_sample_step(B, x_t[0].numel(), objective, step, T, tab, _hip.ptr(t), _hip.ptr(x_t),
+                                          _hip.ptr(out), _hip.ptr(noise), a_next, c, sigma, t_next, _hip.ptr(x_next),
+                                          _hip.ptr(x_start_out), _hip.ptr(t_out), _hip.stream_of(x_t)),
+               "rdq_sample_step")
+
+
+@sample_step.register_fake
+def _(x_t, t, out, noise, tables, objective, step, a_next, c, sigma, t_next, x_next, x_start_out, t_out):
+    return None
 
 
 # ----------------------------------------------------------------------------------------- loop
