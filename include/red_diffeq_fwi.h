@@ -168,6 +168,25 @@ int rdq_fwi_set_handoff_overlap(rdq_fwi_plan *plan, int32_t fwd_mode, int32_t ad
  * cell's arithmetic are the same in both modes: results are bit-identical.  Changing the mode drops the
  * plan's cached graphs. */
 int rdq_fwi_set_wave_roles(rdq_fwi_plan *plan, int32_t fwd_mode, int32_t adj_mode);
+/* Source role of the persistent forward; 0 = every wave runs the generic time loop (RDQ_E_INVALID for any
+ * other mode than those below, nothing changed):
+ *   forward 1 (default): the wave whose rows own the source row is the one every step waits for.  Where that
+ *              row is the receiver row too (isz == igz) and every step is recorded (sample_temporal 1), that
+ *              wave runs every epoch but the last in a loop of its own: a guard-free step plus its real work
+ *              with the row's pair a compile-time constant (one packed add of the source term, the receiver
+ *              value, the wavelet loads and the record), and the waves with neither row run the guard-free
+ *              loop (no source / receiver / history / end-of-record test, no wavelet loads); configs[1]:
+ *              1.034 -> 0.958 ms;
+ *   adjoint:   0 only: every form of the role tried there spilled more registers than the kernel does now.
+ * Built at 4 steps per epoch and 6 rows per wave of the 96-row regions; not run where the source row has a
+ * live halo copy in a neighbouring region, by a call that keeps no history, or at other depths, rows per wave
+ * or region classes: those run the generic loop (rdq_fwi_source_role_info reports the mode that runs).  Per
+ * cell the operations and their order are the same: results are bit-identical in both modes.  Changing the
+ * mode drops the plan's cached graphs. */
+int rdq_fwi_set_source_role(rdq_fwi_plan *plan, int32_t fwd_mode, int32_t adj_mode);
+/* out = {the source-role mode the forward of a call with batch B runs, the same for the adjoint (0)}; 0 for
+ * chunked launches. */
+int rdq_fwi_source_role_info(rdq_fwi_plan *plan, int32_t B, int32_t out[2]);
 /* 1 (default) = run each time loop as ONE persistent launch (regions resident in registers for
  * all nt steps, epoch-wise neighbour hand-offs) whenever the whole grid fits resident on the
  * device: small surveys (at most 200 workgroups, e.g. 3 OpenFWI shots) in 64 x 64 regions of 16

@@ -1226,6 +1226,7 @@ __global__ __launch_bounds__(64 * NW) void k_adj_tw(AdjTBArgs a)
 constexpr int CP_SC1 = 16;                            // buffer cache policy: sc1 (write-through / L1 bypass)
 constexpr int PT_ADJ_SG = 8;                          // adjoint hand-off sweep: rows per load group
 constexpr int PT_ROLES_T = 4;                         // wave roles (rdq_fwi_set_wave_roles) are built at this depth
+constexpr int PT_SROLE_RW = 6;                        // the source role (rdq_fwi_set_source_role): that depth, these rows per wave
 constexpr size_t PROF_RAW = 16;                       // per-wave records after the 11 summary words (PT_PROF_FLUSH)
 constexpr size_t PROF_REC = 8;                        // words per wave record
 constexpr size_t PROF_WAVES = 4096 * 16;              // blocks x waves recorded
@@ -1648,6 +1649,8 @@ struct FwdPtArgs {
     int nt;
     int xcd_mode;                        // 1: XCD-local slices (pt_assign), 0: all hand-offs write-through
     int sweep_delay;                     // s_memrealtime ticks (10 ns) between an epoch's publish and its first sweep pass
+    int srole;                           // source role (rdq_fwi_set_source_role): 1 the plain and the source/receiver
+                                         // waves run loops of their own, 0 every wave the generic loop
 };
 
 // One forward step P_{n+1} = temp1 P_n - temp2 P_{n-1} + alpha N(P_n) (+ source), pde.py:79-81, on
@@ -1668,7 +1671,17 @@ struct FwdPtArgs {
 // store per recorded step (lanes without a receiver at an OOB offset, the record row as the scalar
 // offset), the per-column receiver lists only where a column has several
 #define FWD_RECORD                                                                                  \
-    {                                                                                               \
+    if constexpr (RL_SR >= 0) {                      /* source role: every step exists and is recorded */ \
+        _Pragma("unroll") for (int t = 0; t < T; ++t) {                                             \
+            __builtin_amdgcn_raw_buffer_store_b32(__float_as_uint(rv[t]), SKR, vrec, (n0 + t) * ng4, 0); \
+            unsigned rm_ = rmulti;                                                                  \
+            LAUNDER(rm_);                                                                           \
+            if (rm_ && rec) {                                                                       \
+                float *SK = a.seis + ((size_t)bs * g.nrec + n0 + t) * g.ng;                         \
+                for (int j = rs + 1; j < re; ++j) SK[g.rcv_list[j]] = rv[t];                        \
+            }                                                                                       \
+        }                                                                                           \
+    } else if constexpr (!RL_PLAIN) {                                                               \
         int rrw_ = rrow;                                                                            \
         LAUNDER(rrw_);                                                                              \
         if (rrw_ >= 0) {                                                                            \
@@ -1724,6 +1737,14 @@ __device__ __forceinline__ f32x2 swp(f32x2 v) { return f32x2{v.y, v.x}; }
             const f32x2 a3 = A[i] * lap;                                                            \
             PRV[i] = tt[i] + a3;                                                                    \
         }                                                                                           \
+        if constexpr (RL_SR >= 0) {                  /* source role: the one row's pair is RL_SR */ \
+            if constexpr ((HI) > (LO) && SRP >= (LO) && SRP < (HI)) {                               \
+                float wt_ = wv[t];                                                                  \
+                asm volatile("" : "+s"(wt_));                                                       \
+                const float add = scol ? bsrc * wt_ : -0.0f;                                        \
+                PRV[SRP] = PRV[SRP] + (shalf ? f32x2{-0.0f, add} : f32x2{add, -0.0f});              \
+            }                                                                                       \
+        } else if constexpr (!RL_PLAIN) {            /* (plain role: no source row) */              \
         unsigned sm0_ = (HI) > (LO) ? smask : 0u;                                                  \
         LAUNDER(sm0_);                               /* scalar branch; nothing of it hoisted */     \
         if (sm0_) {                                  /* pde.py:80-81 (uniform: source row waves) */ \
@@ -1746,6 +1767,7 @@ __device__ __forceinline__ f32x2 swp(f32x2 v) { return f32x2{v.y, v.x}; }
                         PT_AT(PRV, r) = PT_AT(PRV, r) + add;                                        \
             }                                                                                       \
         }                                                                                           \
+        }                                                                                           \
     }
 #define FWD_STEP_NB(CUR, PRV)                                                                       \
     {                                                                                               \
@@ -1766,15 +1788,21 @@ __device__ __forceinline__ f32x2 swp(f32x2 v) { return f32x2{v.y, v.x}; }
         if (t + 1 < T) xm_put<NW>(xm, (n + 1) & 1, w, lane, (unsigned)n + 2u, PRV[0], PRV[1]);      \
         __builtin_amdgcn_s_setprio(PT_PRIO_BODY);                                                   \
         FWD_PAIRS_NB(CUR, PRV, 2, RP)                                                                         \
-        if (a.hist && (t + 1 < T || e + 1 == nep)) FWD_HIST(PRV, n)                                 \
-        int rr_ = rrow;                                                                             \
-        LAUNDER(rr_);                                                                               \
-        if (rr_ >= 0) {                              /* receiver row: value kept, stored per epoch */ \
-            int rp_ = rpair;                                                                        \
-            LAUNDER(rp_);                                                                           \
-            f32x2 v_ = PRV[0];                                                                      \
-            _Pragma("unroll") for (int i = 1; i < RP; ++i) if (i == rp_) v_ = PRV[i];                \
-            rv[t] = rhalf ? v_.y : v_.x;                                                            \
+        if constexpr (RL_PLAIN) {                    /* steady epoch of a history-keeping launch */ \
+            if (t + 1 < T) FWD_HIST(PRV, n)                                                         \
+        } else if (a.hist && (t + 1 < T || e + 1 == nep)) FWD_HIST(PRV, n)                          \
+        if constexpr (RL_SR >= 0) {                  /* source role: the receiver row is the source row */ \
+            rv[t] = shalf ? PRV[SRP].y : PRV[SRP].x;                                                \
+        } else if constexpr (!RL_PLAIN) {            /* (plain role: no receiver row) */            \
+            int rr_ = rrow;                                                                         \
+            LAUNDER(rr_);                                                                           \
+            if (rr_ >= 0) {                          /* receiver row: value kept, stored per epoch */ \
+                int rp_ = rpair;                                                                    \
+                LAUNDER(rp_);                                                                       \
+                f32x2 v_ = PRV[0];                                                                  \
+                _Pragma("unroll") for (int i = 1; i < RP; ++i) if (i == rp_) v_ = PRV[i];            \
+                rv[t] = rhalf ? v_.y : v_.x;                                                        \
+            }                                                                                       \
         }                                                                                           \
     }
 
@@ -1845,40 +1873,84 @@ __global__ __launch_bounds__(64 * NW) void k_fwd_pt(FwdPtArgs a)
     xm_init<NW>(xm, w, lane);                             // no flag matches a tag until written
     __syncthreads();
     xm_put<NW>(xm, 0, w, lane, 1u, f32x2{0.0f, 0.0f}, f32x2{0.0f, 0.0f});   // P_0 = 0, step 0's tag
-#define FWD_STEP_SEL FWD_STEP_NB
-    for (int e = 0; e < nep; ++e) {
-        const int n0 = e * T;
-        const __amdgpu_buffer_rsrc_t HFe = rsrc_of(a.hist + (size_t)(n0 + 2) * L + so);   // FWD_HIST
-        PT_PROF_TAIL
-#pragma unroll
-        for (int t = 0; t < T; ++t) {
-            const int n = n0 + t;
-            if (n >= a.nt) break;
-            if (t & 1) FWD_STEP_SEL(P0, P1)
-            else FWD_STEP_SEL(P1, P0)
-        }
-        if (T & 1) {   // keep "P1 = newest" at every epoch boundary
-#pragma unroll
-            for (int i = 0; i < RP; ++i) { const f32x2 tmp = P0[i]; P0[i] = P1[i]; P1[i] = tmp; }
-        }
-        PT_PROF(tst)
-        if (e + 1 < nep) {
-            const unsigned tag = (unsigned)(e + 1);
-            const __amdgpu_buffer_rsrc_t GR = rsrc_of(a.gran + (size_t)(2 * ((e + 1) & 1)) * L + 2 * so);
-            PT_PUBLISH(GR, tag, P0, P1)
-            PT_PROF(tpb)
-            FWD_ISSUE                                     // scalar loads (wav_s): their latency hides in the
-                                                          // delay and the sweep, and no vector op waits on them
-            PT_SWEEP_DELAY()
-            PT_SWEEP(GR, tag, P0, P1, R)
-            if (a.hist) FWD_HIST(P1, n0 + T - 1)          // the epoch's last step (own cells: the sweep
-                                                          // reloads halo cells only)
-            // the next step's boundary rows, with the halo cells the sweep reloaded
-            xm_put<NW>(xm, (n0 + T) & 1, w, lane, (unsigned)(n0 + T) + 1u, P1[0], P1[1]);
-        }
-        FWD_RECORD
+// One epoch e, for the role (RL_PLAIN, RL_SR) in scope.  A role's epoch is steady (never the last: all T
+// steps exist, the hand-off follows) and belongs to a history-keeping launch.  After the steps: keep
+// "P1 = newest"; publish; the next epoch's wavelet samples (scalar loads, wav_s: their latency hides in the
+// delay and the sweep, and no vector op waits on them); the sweep; the epoch's last step's history (own
+// cells: the sweep reloads halo cells only); the next step's boundary rows, with the halo cells the sweep
+// reloaded; the epoch's receiver values.
+#define FWD_EPOCH                                                                                   \
+    {                                                                                               \
+        const int n0 = e * T;                                                                       \
+        const __amdgpu_buffer_rsrc_t HFe = rsrc_of(a.hist + (size_t)(n0 + 2) * L + so);   /* FWD_HIST */ \
+        PT_PROF_TAIL                                                                                \
+        _Pragma("unroll") for (int t = 0; t < T; ++t) {                                             \
+            const int n = n0 + t;                                                                   \
+            if (!RL_PLAIN && n >= a.nt) break;                                                      \
+            if (t & 1) FWD_STEP_NB(P0, P1)                                                          \
+            else FWD_STEP_NB(P1, P0)                                                                \
+        }                                                                                           \
+        if (T & 1) {                                                                                \
+            _Pragma("unroll") for (int i = 0; i < RP; ++i) { const f32x2 tmp = P0[i]; P0[i] = P1[i]; P1[i] = tmp; } \
+        }                                                                                           \
+        PT_PROF(tst)                                                                                \
+        if (RL_PLAIN || e + 1 < nep) {                                                              \
+            const unsigned tag = (unsigned)(e + 1);                                                 \
+            const __amdgpu_buffer_rsrc_t GR = rsrc_of(a.gran + (size_t)(2 * ((e + 1) & 1)) * L + 2 * so); \
+            PT_PUBLISH(GR, tag, P0, P1)                                                             \
+            PT_PROF(tpb)                                                                            \
+            if constexpr (!RL_PLAIN || RL_SR >= 0) { FWD_ISSUE }                                    \
+            PT_SWEEP_DELAY()                                                                        \
+            PT_SWEEP(GR, tag, P0, P1, R)                                                            \
+            if (RL_PLAIN || a.hist) FWD_HIST(P1, n0 + T - 1)                                        \
+            xm_put<NW>(xm, (n0 + T) & 1, w, lane, (unsigned)(n0 + T) + 1u, P1[0], P1[1]);           \
+        }                                                                                           \
+        FWD_RECORD                                                                                  \
     }
-#undef FWD_STEP_SEL
+    // Source role (rdq_fwi_set_source_role), at PT_ROLES_T steps per epoch and 6 rows per wave, in a launch
+    // that keeps its history: a wave branches once, here, into a loop of its own over every epoch but the
+    // last.  A plain wave (no source row, no receiver row) runs steps with no source / receiver / a.hist /
+    // n >= nt test and loads no wavelet samples; the source/receiver wave (its slab owns the one source
+    // row, and that row is its receiver row: isz == igz; every step recorded, the host's test) runs the
+    // plain body plus its own work with the row's pair a compile-time constant: one packed add of the
+    // source term into that pair, the receiver value from it, FWD_ISSUE and FWD_RECORD.  Every other wave
+    // (a source row's halo copy, source and receiver in different rows) and the last epoch of all run the
+    // generic loop.  Mailbox, publish, sweep, zeroing, tags and priorities are the same text, and per cell
+    // the operations and their order: results are bit for bit those of mode 0.
+    int e = 0;
+    constexpr bool RL_PLAIN = false;                      // the generic role (shadowed in the role loops)
+    constexpr int RL_SR = -1, SRP = 0;                    // source role: the row's pair (SRP = max(RL_SR, 0))
+    if constexpr (T == PT_ROLES_T && RW == PT_SROLE_RW) {
+        int role = 0;                                     // 0 generic, 1 plain, 2 + pair: source/receiver
+        if (a.srole && a.hist) {
+            if (smask == 0 && rrow < 0) role = 1;
+            else if (s1row && rrow == sr1) role = 2 + spair;
+        }
+        role = __builtin_amdgcn_readfirstlane(role);
+        if (role == 1) {
+            constexpr bool RL_PLAIN = true;
+            for (; e + 1 < nep; ++e) FWD_EPOCH            // (no source row: the generic epoch reads no sample)
+        } else if (role == 2) {
+            constexpr bool RL_PLAIN = true;
+            constexpr int RL_SR = 0, SRP = 0;
+            for (; e + 1 < nep; ++e) FWD_EPOCH
+        } else if (role == 3) {
+            constexpr bool RL_PLAIN = true;
+            constexpr int RL_SR = 1, SRP = 1;
+            for (; e + 1 < nep; ++e) FWD_EPOCH
+        } else if (role == 4) {
+            constexpr bool RL_PLAIN = true;
+            constexpr int RL_SR = 2, SRP = 2;
+            for (; e + 1 < nep; ++e) FWD_EPOCH
+        }
+        // Where the loops meet the samples must stay scalars: without this the compiler merges them in VGPRs
+        // and the generic step's SGPR constraint on wv[t] does not compile ("illegal VGPR to SGPR copy").
+        // Uniform by construction; once per launch.
+#pragma unroll
+        for (int t = 0; t < T; ++t) wv[t] = __int_as_float(__builtin_amdgcn_readfirstlane(__float_as_int(wv[t])));
+    }
+    for (; e < nep; ++e) FWD_EPOCH
+#undef FWD_EPOCH
 #undef FWD_ISSUE
     PT_PROF_TAIL
     PT_PROF_FLUSH
@@ -2413,7 +2485,9 @@ __global__ __launch_bounds__(64 * NW) void k_adj_pr(AdjPtArgs a)
     // the other waves and the last epoch of all.  Mailbox, publish, sweep, zeroing and tags are the same
     // text in both, and per cell the arithmetic is the same: results are bit for bit those of mode 0.
     // configs[1]: 1.4464 -> 1.4193 ms (profiles/r11/kernel_ab_adj_roles.jsonl).  (One loop choosing a body
-    // per epoch spilled 107 VGPRs; the same split of the forward's steps was no faster and is not built.)
+    // per epoch spilled 107 VGPRs; the same split of the forward's steps alone was no faster: the forward has
+    // it with its source role, k_fwd_pt.  A source role here spilled 11 to 413 values in the three forms tried,
+    // profiles/r13/resource_usage.txt, and is not built.)
     int e = 0;
     if constexpr (T == PT_ROLES_T) {
         if (plain) {
@@ -2801,6 +2875,8 @@ constexpr int RDQ_SWEEP_DELAY_FWD = 15, RDQ_SWEEP_DELAY_ADJ = 0;
 // default hand-off overlap mode of the persistent adjoint (rdq_fwi_set_handoff_overlap); mode 1 exists at
 // PT_OV_T steps per epoch
 constexpr int RDQ_OVERLAP_ADJ = 1, PT_OV_T = 4;
+// default source-role mode of the persistent forward (rdq_fwi_set_source_role)
+constexpr int RDQ_SROLE_FWD = 1;
 
 struct rdq_fwi_plan {
     rdq_fwi_geom g;
@@ -2830,6 +2906,7 @@ struct rdq_fwi_plan {
     int fwd_delay = RDQ_SWEEP_DELAY_FWD, adj_delay = RDQ_SWEEP_DELAY_ADJ;   // persistent kernels' pre-sweep delay (ticks)
     int adj_ov = RDQ_OVERLAP_ADJ;   // the persistent (recurrence) adjoint's hand-off overlap mode
     int adj_roles = 1;              // wave roles of the persistent (recurrence) adjoint (rdq_fwi_set_wave_roles)
+    int fwd_srole = RDQ_SROLE_FWD;  // source role of the persistent forward (rdq_fwi_set_source_role)
     int adj_Tw = 0;             // the wide chunked adjoint's depth (<= TW_ADJ_MAXT); 0 = auto, see wide_adj_depth
     int fwd_Tw = 0;             // the wide chunked forward's depth (<= TW_FWD_MAXT); 0 = auto, see wide_fwd_depth
     int adj_spw = 0;            // the wide chunked adjoint's shots per workgroup, 0 = auto (wide_spw)
@@ -3177,6 +3254,30 @@ int adj_overlap(const rdq_fwi_plan *p) { return p->adj_T == PT_OV_T && p->adj_fm
 // The wave-role mode the persistent adjoint runs (0 = every wave the generic loop): the plain role is built
 // at PT_ROLES_T steps per epoch, in the recurrence adjoint.
 int adj_wave_roles(const rdq_fwi_plan *p) { return p->adj_T == PT_ROLES_T && p->adj_fma ? p->adj_roles : 0; }
+// Whether a persistent launch of region class NW at depth T and `rw` rows per wave has a source/receiver
+// wave (the source role, rdq_fwi_set_source_role): 96-row regions at PT_SROLE_RW rows per wave and PT_ROLES_T
+// steps per epoch, source and receivers in one padded row, every step recorded, and the source row held by
+// its owning region alone.  A live halo copy of it in the neighbouring region (a row of that region's
+// dependence cone: PT_REGION_GEOM's rcy) repeats the source add in the generic loop every step, on the same
+// path, so there the role is not run.
+bool source_role_fits(const rdq_fwi_plan *p, int NW, int T, int rw)
+{
+    if (NW != 12 || T != PT_ROLES_T || rw != PT_SROLE_RW) return false;
+    if (p->g.isz != p->g.igz || p->g.sample_temporal != 1) return false;
+    const int H = 2 * T, RH = 96, IH = RH - 2 * H;       // the 96-row class (region_rows)
+    for (int ty = 0; ty * IH < p->Hp; ++ty) {
+        const int vh = std::min(IH, p->Hp - ty * IH);
+        for (int rr = 0; rr < RH; ++rr) {
+            const int uz = ty * IH - H + rr;
+            const bool own = rr >= H && rr < RH - H && uz < p->Hp;
+            if (((uz % p->Hp) + p->Hp) % p->Hp == p->g.isz && !own && rr - H < vh + H) return false;
+        }
+    }
+    return true;
+}
+// The source-role mode a persistent forward launch runs (0 = none); it covers the plain loop too.  (A no-grad
+// call keeps no history and runs the generic loop whatever the mode.)
+int fwd_source_role(const rdq_fwi_plan *p, int NW) { return p->fwd_srole && source_role_fits(p, NW, p->fwd_T, p->fwd_rw); }
 KernelRef<AdjPtArgs> adj_pt_kernel(const rdq_fwi_plan *p, int NW, int T, bool fma, bool prof)
 {
     static_assert(PT_OV_T == 4, "the profiled and the overlap builds share their depth");
@@ -3382,6 +3483,7 @@ int launch_forward_pt(rdq_fwi_plan *p, int B, int NW, int per, const float *coef
     a.gran = reinterpret_cast<unsigned long long *>(ring);
     a.status = p->d_status; a.nt = p->g.nt; a.prof = p->d_prof; a.xcd_mode = p->xcd_mode;
     a.sweep_delay = p->fwd_delay;
+    a.srole = fwd_source_role(p, NW);
     // consecutive slice groups, one resident launch each (granules live at per-slice offsets, so
     // one zeroing serves every group)
     for (int s0 = 0; s0 < B * p->g.ns; s0 += per) {
@@ -3940,6 +4042,24 @@ int rdq_fwi_set_wave_roles(rdq_fwi_plan *p, int32_t fwd_mode, int32_t adj_mode)
     if (!p || fwd_mode != 0 || adj_mode < 0 || adj_mode > 1) return RDQ_E_INVALID;
     std::lock_guard<std::mutex> lk(p->mu);
     set_knob(p, p->adj_roles, adj_mode);   // (drops the cached graphs when the value changes)
+    return 0;
+}
+
+int rdq_fwi_set_source_role(rdq_fwi_plan *p, int32_t fwd_mode, int32_t adj_mode)
+{
+    if (!p || fwd_mode < 0 || fwd_mode > 1 || adj_mode != 0) return RDQ_E_INVALID;   // the adjoint has no such role
+    std::lock_guard<std::mutex> lk(p->mu);
+    set_knob(p, p->fwd_srole, fwd_mode);   // (drops the cached graphs when the value changes)
+    return 0;
+}
+
+int rdq_fwi_source_role_info(rdq_fwi_plan *p, int32_t B, int32_t out[2])
+{
+    if (!p || !out || B < 1) return RDQ_E_INVALID;
+    std::lock_guard<std::mutex> lk(p->mu);
+    const int nwf = persistent_nw(p, B, false);
+    out[0] = nwf ? fwd_source_role(p, nwf) : 0;
+    out[1] = 0;   // the adjoint has the generic and the plain loop only
     return 0;
 }
 

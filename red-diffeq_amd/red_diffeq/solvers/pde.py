@@ -159,15 +159,19 @@ class FwiPlan:
         """{'fwd_persistent', 'adj_persistent', 'fwd_class' / 'adj_class' (persistent region class: 16 /
         12 / 8, 0 = chunked), 'fwd_T', 'adj_T', 'fwd_launches', 'adj_launches', 'fwd_overlap' /
         'adj_overlap' (the hand-off overlap mode that runs, set_handoff_overlap), 'fwd_roles' /
-        'adj_roles' (the wave-role mode that runs, set_wave_roles)} of a
+        'adj_roles' (the wave-role mode that runs, set_wave_roles), 'fwd_src_role' / 'adj_src_role' (the
+        source-role mode that runs, set_source_role)} of a
         call with batch B (launches: time-loop kernel launches per call)."""
         out = (ctypes.c_int32 * 10)()
         _hip.check(self.lib.rdq_fwi_launch_info(self.handle, int(B), out), "rdq_fwi_launch_info")
+        src = (ctypes.c_int32 * 2)()
+        _hip.check(self.lib.rdq_fwi_source_role_info(self.handle, int(B), src), "rdq_fwi_source_role_info")
         return {"fwd_persistent": bool(out[0]), "adj_persistent": bool(out[1]),
                 "fwd_class": int(out[0]), "adj_class": int(out[1]), "fwd_T": int(out[2]),
                 "adj_T": int(out[3]), "fwd_launches": int(out[4]), "adj_launches": int(out[5]),
                 "fwd_overlap": int(out[6]), "adj_overlap": int(out[7]),
-                "fwd_roles": int(out[8]), "adj_roles": int(out[9])}
+                "fwd_roles": int(out[8]), "adj_roles": int(out[9]),
+                "fwd_src_role": int(src[0]), "adj_src_role": int(src[1])}
 
     def set_sweep_delay(self, fwd_ticks, adj_ticks):
         """Persistent kernels: 10 ns ticks between an epoch's publish and its first hand-off pass."""
@@ -187,6 +191,15 @@ class FwiPlan:
         wave runs the generic loop.  The forward has mode 0 only.  Results are bit-identical in both modes."""
         _hip.check(self.lib.rdq_fwi_set_wave_roles(self.handle, int(fwd_mode), int(adj_mode)),
                    "rdq_fwi_set_wave_roles")
+
+    def set_source_role(self, fwd_mode, adj_mode):
+        """Persistent forward at 4 steps per epoch and 6 rows per wave, source and receivers in one row: 1
+        (default) = the wave that owns that row runs every epoch but the last in a loop of its own (a
+        guard-free step plus the row's own work) and the waves with neither row a guard-free loop, 0 = the
+        generic loop.  The adjoint has mode 0 only.  launch_info reports the mode that runs.  Results are
+        bit-identical in both modes."""
+        _hip.check(self.lib.rdq_fwi_set_source_role(self.handle, int(fwd_mode), int(adj_mode)),
+                   "rdq_fwi_set_source_role")
 
     def wide_info(self, B):
         """{'chains', 'fwd_spw', 'adj_spw', 'chain0_shots'}: the wide chunked kernels' concurrent launch
