@@ -304,6 +304,42 @@ int rdq_fwi_adjoint_ckpt(const rdq_fwi_plan *plan, int32_t B, int32_t K, const f
  * per launch chain, backward time-loop launches per chain (every segment's recompute and adjoint)}. */
 int rdq_fwi_ckpt_info(rdq_fwi_plan *plan, int32_t B, int32_t K, int32_t out[4]);
 
+/* Linearised (Born) forward: dseis = J dv, J = d(seis)/d(v) at the model `coeffs` was made from; with K2 + K4
+ * (which apply J^T) the Gauss-Newton product J^T W J dv.
+ *   Equations.  The forward step is P_{n+1} = T1 P_n - T2 P_{n-1} + A Lap(P_n) + beta_src w[n], T1 = 2 + 2 c1 A - K,
+ *   T2 = 1 - K, Lap = c2 S1 + c3 S2 (the four nearest and the four second neighbours, periodic wrap).  Its tangent is
+ *     dP_{n+1} = T1 dP_n - T2 dP_{n-1} + A Lap(dP_n) + dA (2 c1 P_n + Lap(P_n)) - dK (P_n - P_{n-1}) + dbeta_src w[n],
+ *   dP_0 = dP_{-1} = 0, recorded at the receivers when n % sample_temporal == 0, where the forward records, with
+ *     dA    = 2 v (dt/dx)^2 dv   on the padded grid, dv replicate-padded (the clamped model index, as K3 reads v),
+ *     dbeta = 2 v dt^2 dv        at each source cell,
+ *     dK    = K dv[argmin] / vmin: the sponge is linear in vmin (pde.py:41-46) and torch.min passes the tangent of
+ *             the first row-major argmin only, the cell `vstat` holds,
+ *   and dv = 1500 dv_norm under RDQ_VEL_NORMALIZED.  The two bracketed terms are the ones whose transposes K2
+ *   accumulates into gA and gk_part.
+ *   Scale.  J is linear, so the prologue brings each model's direction to a fixed magnitude with a power of two
+ *   (dvs = dv 2^-k, max |dvs| in [2^-64, 2^-63)) and the time loop multiplies what it records by 2^k: the loop runs
+ *   on the same bits whatever the magnitude of dv, and for max |dv| >= 2^-64 the rescale is exact.
+ *   Layout.  `dwork` (rdq_fwi_born_sizes bytes) is float dam [B][nz][nx] (dA per model cell, from dvs in m/s; a
+ *   padded cell reads the model cell its clamped index names), then ratio [B] (dvs[argmin] / vmin), dbeta [B][ns],
+ *   oscale [B] (2^k) and uint32 dmax [B] (the bits of max |dv|);
+ *   rdq_fwi_dcoeffs, the prologue, writes it from a direction
+ *   dv[b][0][iz][ix] given by element strides (any view, as rdq_fwi_coeffs reads v) and the `coeffs` / `vstat` of
+ *   rdq_fwi_coeffs for the same model.  `history` is the store-all history rdq_fwi_forward kept for the same
+ *   `coeffs` (slot j = P_{j-1}); `dseis_out` is float [B][ns][nrec][ng] like seis; `ring` as for rdq_fwi_forward
+ *   (its four levels carry dP between launches; one buffer may serve every call).
+ *   rdq_fwi_born always runs the narrow chunked kernels at rdq_fwi_set_tuning's fwd_steps and chains, whatever
+ *   rdq_fwi_set_persistent or RDQ_VARIANT_NARROW_CHUNKED say (RDQ_VARIANT_FWD_GEN chooses its coefficient source as
+ *   for the forward), under the one-call-in-flight rule of the other time loops.  One fixed fp32 operation order (no
+ *   contraction; written next to the kernel): dseis is bit-identical for every depth, chain count and graph
+ *   setting, and J (2^j dv) = 2^j J dv bit for bit while max |dv| >= 2^-64 on both sides.  RDQ_E_INVALID for a
+ *   null argument or B < 1. */
+int rdq_fwi_born_sizes(const rdq_fwi_plan *plan, int32_t B, size_t *bytes);
+int rdq_fwi_dcoeffs(const rdq_fwi_plan *plan, int32_t B, const float *dv, const int64_t strides[4],
+                    int32_t vel_mode, const float *coeffs, const void *vstat, float *dwork,
+                    hipStream_t stream);
+int rdq_fwi_born(const rdq_fwi_plan *plan, int32_t B, const float *coeffs, const float *dwork,
+                 const float *history, float *dseis_out, float *ring, hipStream_t stream);
+
 /* K4: d(loss)/d(v) [B][nz][nx] (contiguous) from the accumulators: chain through
  * alpha/beta/sponge(vmin), replicate-pad fold, and (RDQ_VEL_NORMALIZED) the x1500 of the
  * denormalisation. */

@@ -8,6 +8,8 @@
 //                          the survey fits resident (k_fwd_pt), else launches of T steps (k_fwd_tb)
 //   K2 rdq_fwi_adjoint     the autograd backward of pde.py:74-86 (discrete adjoint)
 //   K4 rdq_fwi_grad_finalize  chain rule back to v_norm incl. the vmin/argmin sponge term
+//   -- rdq_fwi_dcoeffs / rdq_fwi_born  torch.func.jvp of pde.py:88-93 in a direction dv: the linearised (Born)
+//                          forward over K1's stored history (k_dcoeffs, k_born_tb)
 //
 // fp32 operation order follows the reference expression order exactly and the file is built
 // with -ffp-contract=off, so K1 reproduces the reference seismograms bit-for-bit and K2's
@@ -767,6 +769,260 @@ __global__ __launch_bounds__(64 * TB_NW, 4) void k_adj_tb(AdjTBArgs a)
         __syncthreads();
     }
     if (tid == 0) a.gk_part[(size_t)bs * a.nblk + ti.tile] += red[0];
+}
+
+// --------------------------------------------------------------------------------------- Born
+// Linearised forward J dv (rdq_fwi_born).  The tangent of the time step in the direction dv,
+//   dP_{n+1} = T1 dP_n - T2 dP_{n-1} + A Lap(dP_n) + dA (2c1 P_n + Lap(P_n)) - dK (P_n - P_{n-1}) + dbeta_src w[n],
+// dP_0 = dP_{-1} = 0, recorded at the receivers where the forward records.  The two bracketed terms are the ones
+// whose transposes k_adj_tb accumulates into gA and gk_part.
+//
+// Scale.  J is linear, so each model's direction is brought to a fixed magnitude by a power of two before anything
+// is derived from it, dvs = dv 2^-k with max |dvs| in [2^-64, 2^-63), and the record is multiplied by 2^k where it
+// is stored.  The time loop then runs on the same bits whatever the magnitude of dv (no direction is too small to
+// linearise, none overflows), and for max |dv| >= 2^-64 the rescale is an up-scale, which is exact: J (2^j dv) =
+// 2^j J dv bit for bit.  (Without it the equality breaks wherever the tangent field is near the underflow
+// threshold: measured at the 88 x 118 test grid, 1575 of 23040 recorded values, all below 1e-13 of the record's
+// peak.)  2^-64 leaves the loop 85 binades between a unit response and the smallest denormal; fp32 resolves 24.
+//
+// Perturbation workspace (rdq_fwi_born_sizes; written by the prologue, k_dmax + k_dcoeffs):
+//   dam    [B][nz][nx]  dA per model cell, (2 (v dt / dx)) ((dvs dt) / dx) with dvs in m/s (x1500 of a normalised
+//                       one): a padded cell's dA is that of the model cell its clamped index names (the replicate
+//                       pad), so the divisions are done once per model cell here, not per padded cell, shot and launch
+//   ratio  [B]          dvs[argmin] / vmin: the sponge is linear in vmin and torch.min passes the tangent of the
+//                       first row-major argmin only, the cell K3 leaves in vstat
+//   dbeta  [B][ns]      2 (v dt)(dvs dt) at each source cell
+//   oscale [B]          2^k, the record's rescale
+//   dmax   [B]          bits of max |dv| over the model (uint32, zeroed, then atomic max: order-free)
+struct DCoefArgs {
+    const float *dv;                     // the caller's direction, element strides s0 / s2 / s3 (as k_coeffs reads v)
+    int64_t s0, s2, s3;
+    int vel_mode, B, nz, nx, ns, nbc, isz, ld;
+    float dt, dx;
+    size_t slice, cstride;
+    const float *coeffs;                 // K3 fields (v at 5 x cstride)
+    const float *vmod;                   // K3's model copy [B][nz][nx] (m/s)
+    const float *vmin;
+    const int64_t *amin;
+    const int *isx;
+    float *dam, *ratio, *dbeta, *oscale;
+    unsigned *dmax;
+};
+
+// max |dv| of each model, as the bits of a non-negative float (they order as the values do); grid (parts, B)
+__global__ __launch_bounds__(256) void k_dmax(DCoefArgs p)
+{
+    const int b = blockIdx.y, n = p.nz * p.nx;
+    unsigned m = 0;
+    for (int i = blockIdx.x * blockDim.x + threadIdx.x; i < n; i += gridDim.x * blockDim.x) {
+        const int iz = i / p.nx, ix = i - iz * p.nx;
+        m = max(m, __float_as_uint(p.dv[b * p.s0 + iz * p.s2 + ix * p.s3]) & 0x7fffffffu);
+    }
+    __shared__ unsigned sm[256];
+    sm[threadIdx.x] = m;
+    __syncthreads();
+    for (int w = 128; w > 0; w >>= 1) {
+        if (threadIdx.x < w) sm[threadIdx.x] = max(sm[threadIdx.x], sm[threadIdx.x + w]);
+        __syncthreads();
+    }
+    if (threadIdx.x == 0) atomicMax(&p.dmax[b], sm[0]);
+}
+
+// biased exponent of max |dv|, kept where both powers of two below are normal floats
+__device__ __forceinline__ unsigned dcoef_exp(const DCoefArgs &p, int b) { return min(p.dmax[b] >> 23, 189u); }
+
+__device__ __forceinline__ float dcoef_dv(const DCoefArgs &p, int b, int iz, int ix)
+{
+    float d = p.dv[b * p.s0 + iz * p.s2 + ix * p.s3];
+    d = d * __uint_as_float((190u - dcoef_exp(p, b)) << 23);   // 2^-k: max |d| into [2^-64, 2^-63), exact
+    if (p.vel_mode == 0) d = d * 1500.0f;          // tangent of data_trans.py:15: ((v + 1) / 2) * 3000 + 1500
+    return d;
+}
+
+__global__ __launch_bounds__(256) void k_dcoeffs(DCoefArgs p)
+{
+    const int n = p.nz * p.nx, nm = p.B * n;
+    const int i = blockIdx.x * blockDim.x + threadIdx.x;
+    if (i < nm) {
+        const int b = i / n, c = i - b * n, iz = c / p.nx, ix = c - iz * p.nx;
+        float x = p.vmod[i] * p.dt; x = x / p.dx; x = 2.0f * x;         // tangent of pde.py:63, (v dt / dx)^2
+        float d = dcoef_dv(p, b, iz, ix) * p.dt; d = d / p.dx;
+        p.dam[i] = x * d;
+    } else if (i < nm + p.B) {
+        const int b = i - nm;
+        const int c = (int)p.amin[b], iz = c / p.nx, ix = c - iz * p.nx;
+        p.ratio[b] = dcoef_dv(p, b, iz, ix) / p.vmin[b];
+        p.oscale[b] = __uint_as_float((dcoef_exp(p, b) + 64u) << 23);   // 2^k
+    } else if (i < nm + p.B + p.B * p.ns) {
+        const int j = i - nm - p.B, b = j / p.ns, s = j - b * p.ns;
+        const int iz = min(max(p.isz - p.nbc, 0), p.nz - 1), ix = min(max(p.isx[s] - p.nbc, 0), p.nx - 1);
+        const float v = p.coeffs[5 * p.cstride + (size_t)b * p.slice + (size_t)p.isz * p.ld + p.isx[s]];
+        float bt = v * p.dt; bt = 2.0f * bt;                            // tangent of pde.py:71, (v dt)^2
+        const float dbt = dcoef_dv(p, b, iz, ix) * p.dt;
+        p.dbeta[j] = bt * dbt;
+    }
+}
+
+struct BornTBArgs {
+    TBGeo g;
+    CoefGen cg;                          // model + sponge amplitude (GEN variant)
+    const float *coeffs;                 // K3 fields: alpha, kappa at 0, 3 x cstride
+    const float *in_prev, *in_cur;       // dP_{n-1}, dP_n
+    float *out_prev, *out_cur;           // dP_{n+T-1}, dP_{n+T}
+    const float *hist;                   // the forward's store-all history, slot j = P_{j-1}
+    const float *dam, *ratio, *dbeta, *oscale;   // perturbation workspace (above)
+    float *dseis;
+    int n0, nsteps;
+    float w[TB_MAXT];                    // wavelet samples w[n0 .. n0+nsteps-1]
+};
+
+// The narrow chunked layout of k_fwd_tb / k_adj_tb: 64 columns x 8 waves x 8 rows in registers, halo 2T.  dP is
+// carried as the forward carries P (two levels in, two out, through the ring); P_n streams from the history as in
+// k_adj_tb: buffer loads, prefetched one step ahead, out-of-range offsets on the rows no live cell reads (at
+// step t of a launch the live cells are the region less 2 (t + 1) on every side, their P taps less 2 t), halo rows
+// through the second LDS exchange.  The level before, P_{n-1}, is the previous step's registers.  dA is read once
+// per launch from the dam cell gen_coef's clamped index names (the replicate pad), dK = K ratio per use.
+//
+// Operation order (contraction off), per cell and step; S1 / S2 = the four nearest / second neighbours summed as
+// ((up + down) + left) + right:
+//   lap  = C2 S1(dP_n) + C3 S2(dP_n)
+//   hom  = (T1 dP_n - T2 dP_{n-1}) + A lap                              the forward's own order
+//   d    = 2c1 P_n + (C2 S1(P_n) + C3 S2(P_n))                          k_adj_tb's gA factor
+//   f    = dA d - (K ratio)(P_n - P_{n-1})
+//   dP_{n+1} = hom + f, then + dbeta w[n] at the source cell
+// with dA from the prologue; a recorded value is stored as dP 2^k (the scale above).
+template <int T, bool GEN>
+__global__ __launch_bounds__(64 * TB_NW) void k_born_tb(BornTBArgs a)
+{
+    constexpr int H = 2 * T, IW = 64 - 2 * H, IH = TB_RH - 2 * H;
+    __shared__ float xch[2][TB_NW][4][64];
+    __shared__ float pxc[2][TB_NW][4][64];
+    const TBGeo &g = a.g;
+    const int lane = threadIdx.x & 63;
+    const int w = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);   // wave-uniform
+    const TileId ti = decode_tile(blockIdx.x, g.tiles_x, g.ntiles, g.B * g.ns_grp);
+    if (!ti.valid) return;                                            // whole workgroup: uniform
+    const int b = ti.sl / g.ns_grp, s = g.s_off + (ti.sl - b * g.ns_grp), bs = b * g.ns + s;
+    const int ux = ti.tx * IW - H + lane;
+    const int gx = wrapn(ux, g.Wp);
+    const bool xin = lane >= H && lane < 64 - H && ux < g.Wp;
+    const int uz0 = ti.ty * IH - H + w * TB_R;
+    const size_t so = (size_t)bs * g.slice;
+    const float *AL = a.coeffs + (size_t)b * g.slice;
+    const float *KAp = AL + 3 * g.cstride;
+    const int isx = g.isx[s];
+    const float ratio = a.ratio[b], oscale = a.oscale[b];
+    float A[TB_R], K[TB_R], dA[TB_R], D0[TB_R], D1[TB_R];
+    float Q[3][TB_R];               // history levels in rotation: step t reads P_{n-1} = Q[t % 3], P_n = Q[(t + 1) % 3]
+    int rofs[TB_R], pofs[TB_R];
+    unsigned rin = 0, smask = 0;    // wave-uniform row masks: interior and inside the domain; the source row
+    int rrow = -1;                  // wave-uniform: row holding the receivers
+#pragma unroll
+    for (int r = 0; r < TB_R; ++r) {
+        const int uz = uz0 + r, gz = wrapn(uz, g.Hp);
+        rofs[r] = gz * g.ld;
+        const int o = rofs[r] + gx;
+        pofs[r] = o * 4;
+        if constexpr (GEN) {
+            const Coef cf = gen_coef(a.cg, b, gz, gx);
+            A[r] = cf.al; K[r] = cf.kp;
+        } else {
+            A[r] = AL[o]; K[r] = KAp[o];
+        }
+        const int iz = min(max(gz - a.cg.nbc, 0), a.cg.nz - 1), ix = min(max(gx - a.cg.nbc, 0), a.cg.nx - 1);
+        dA[r] = a.dam[((size_t)b * a.cg.nz + iz) * a.cg.nx + ix];
+        D0[r] = a.in_prev[so + o];
+        D1[r] = a.in_cur[so + o];
+        const int rr = w * TB_R + r;
+        if (rr >= H && rr < TB_RH - H && uz < g.Hp) rin |= 1u << r;
+        if (gz == g.isz) smask |= 1u << r;      // a region taller than a tiny domain holds the row more than once
+        if (gz == g.igz) rrow = r;
+    }
+    const bool scol = gx == isx;
+    const float dbsrc = smask ? a.dbeta[bs] : 0.0f;
+    const int rs = (rrow >= 0) ? g.rcv_start[gx] : 0, re = (rrow >= 0) ? g.rcv_start[gx + 1] : 0;
+    const int rcv0 = rs < re ? g.rcv_list[rs] : -1;
+    const bool rmulti = __any(re - rs > 1);               // wave-uniform: a column with several receivers
+    const int slice_bytes = (int)(g.slice * 4);
+    {   // slots n0, n0 + 1 = P_{n0-1}, P_{n0}: every row (step 0's taps reach the region's edge)
+        const __amdgpu_buffer_rsrc_t H0 = rsrc_of(a.hist + (size_t)a.n0 * g.level + so, slice_bytes);
+        const __amdgpu_buffer_rsrc_t H1 = rsrc_of(a.hist + (size_t)(a.n0 + 1) * g.level + so, slice_bytes);
+#pragma unroll
+        for (int r = 0; r < TB_R; ++r) { Q[0][r] = bload(H0, pofs[r], 0); Q[1][r] = bload(H1, pofs[r], 0); }
+    }
+#pragma unroll
+    for (int t = 0; t < T; ++t) {
+        if (t >= a.nsteps) break;
+        const int n = a.n0 + t;
+        float *cur = (t & 1) ? D0 : D1;     // dP_n
+        float *prv = (t & 1) ? D1 : D0;     // dP_{n-1} -> overwritten with dP_{n+1}
+        const float *Pp = Q[t % 3], *P = Q[(t + 1) % 3];
+        float *Pn = Q[(t + 2) % 3];
+        if (t + 1 < a.nsteps) {             // P_{n+1} on the rows step t + 1's taps read
+            const __amdgpu_buffer_rsrc_t HR = rsrc_of(a.hist + (size_t)(n + 2) * g.level + so, slice_bytes);
+#pragma unroll
+            for (int r = 0; r < TB_R; ++r) {
+                const int rr = w * TB_R + r;
+                Pn[r] = bload(HR, (rr >= 2 * (t + 1) && rr < TB_RH - 2 * (t + 1)) ? pofs[r] : OOB, 0);
+            }
+        }
+        Halo4 hd, hp;
+        const float de[4] = {cur[0], cur[1], cur[TB_R - 2], cur[TB_R - 1]};
+        const float pe[4] = {P[0], P[1], P[TB_R - 2], P[TB_R - 1]};
+        exchange2(xch, pxc, t & 1, w, lane, de, pe, hd, hp);
+#pragma unroll
+        for (int r = 0; r < TB_R; ++r) {
+            TB_VERT(cur, r, hd, zm2, zm1, zp1, zp2)
+            const float c = cur[r];
+            const float xl1 = dpp_shr1(c), xr1 = dpp_shl1(c);
+            const float xl2 = dpp_shr1(xl1), xr2 = dpp_shl1(xr1);
+            float s1 = zm1 + zp1; s1 = s1 + xl1; s1 = s1 + xr1;
+            float s2 = zm2 + zp2; s2 = s2 + xl2; s2 = s2 + xr2;
+            float lap = C2 * s1; const float l2 = C3 * s2; lap = lap + l2;
+            const float kp = K[r];
+            float t1 = C1X2 * A[r]; t1 = t1 + 2.0f; t1 = t1 - kp;     // pde.py:69
+            const float t2 = 1.0f - kp;                               // pde.py:70
+            float hom = t1 * c; const float a2 = t2 * prv[r]; hom = hom - a2;
+            const float a3 = A[r] * lap; hom = hom + a3;
+            TB_VERT(P, r, hp, pm2, pm1, pp1, pp2)
+            const float pc = P[r];
+            const float pl1 = dpp_shr1(pc), pr1 = dpp_shl1(pc);
+            const float pl2 = dpp_shr1(pl1), pr2 = dpp_shl1(pr1);
+            float q1 = pm1 + pp1; q1 = q1 + pl1; q1 = q1 + pr1;
+            float q2 = pm2 + pp2; q2 = q2 + pl2; q2 = q2 + pr2;
+            float plap = C2 * q1; const float pq = C3 * q2; plap = plap + pq;
+            float d = C1X2 * pc; d = d + plap;
+            float f = dA[r] * d;
+            const float dk = kp * ratio, dp = pc - Pp[r];
+            const float fk = dk * dp; f = f - fk;
+            prv[r] = hom + f;
+        }
+        if (smask) {
+#pragma unroll
+            for (int r = 0; r < TB_R; ++r)
+                if ((smask & (1u << r)) && scol) { const float add = dbsrc * a.w[t]; prv[r] = prv[r] + add; }
+        }
+        if (rrow >= 0 && (rin & (1u << rrow)) && xin && (n % g.st) == 0) {   // pde.py:82-83
+            float val = 0.0f;
+#pragma unroll
+            for (int r = 0; r < TB_R; ++r) if (r == rrow) val = prv[r];
+            val = val * oscale;
+            float *SK = a.dseis + ((size_t)bs * g.nrec + n / g.st) * g.ng;
+            if (rcv0 >= 0) SK[rcv0] = val;
+            if (rmulti)
+                for (int j = rs + 1; j < re; ++j) SK[g.rcv_list[j]] = val;
+        }
+    }
+    if (xin) {
+        const bool odd = (a.nsteps & 1) != 0;   // after nsteps steps the newest level is in D0 if odd
+#pragma unroll
+        for (int r = 0; r < TB_R; ++r)
+            if (rin & (1u << r)) {
+                const size_t o = so + rofs[r] + gx;
+                a.out_cur[o] = odd ? D0[r] : D1[r];
+                a.out_prev[o] = odd ? D1[r] : D0[r];
+            }
+    }
 }
 
 // --------------------------------------------------------------------------------------- K1/K2
@@ -2862,7 +3118,7 @@ __global__ __launch_bounds__(256) void k_smooth_bwd(int kind, int H, int W, cons
 
 // ======================================================================================= plan
 struct GraphEntry {
-    int kind;                 // 0 fwd-history, 1 fwd-ring, 2 adjoint, 3 fwd-checkpoint, 4 adjoint-checkpoint
+    int kind;                 // 0 fwd-history, 1 fwd-ring, 2 adjoint, 3 fwd-checkpoint, 4 adjoint-checkpoint, 5 born
     int B;
     int K;                    // checkpoint interval (kinds 3, 4; else 0): it shapes the launch sequence
     const void *ptrs[8];
@@ -2962,11 +3218,12 @@ TBGeo tb_geo(const rdq_fwi_plan *p, int B)
 // launches fill the other's tail rounds: configs[4] forward 54.7 -> 49.0-50.0 ms, adjoint 93.8 ->
 // 91.0-91.6; 3 / 4 / 8 chains 51.7 / 53.9 / 58.0 and 93.1 / 95.1 / 101.2; profiles/r5/configs4_chains.jsonl),
 // one for the 64-column kernels.
-int chain_count(const rdq_fwi_plan *p)
+int chain_count(const rdq_fwi_plan *p, bool wide)
 {
-    const int c = p->chains > 0 ? p->chains : (p->wide ? 2 : 1);
+    const int c = p->chains > 0 ? p->chains : (wide ? 2 : 1);
     return std::max(1, std::min(c, p->g.ns));
 }
+int chain_count(const rdq_fwi_plan *p) { return chain_count(p, p->wide); }
 
 // Default depth of the wide chunked adjoint, measured at configs[4] (profiles/r5/configs4_wide_adj_depth.jsonl):
 // 5 steps per launch is the fastest for both forms (exact order 116.1-116.3 ms vs 120.4 at 4 and 120.6
@@ -3158,6 +3415,12 @@ KernelRef<FwdTBArgs> fwd_tb_kernel(int T, bool gen)
 KernelRef<AdjTBArgs> adj_tb_kernel(int T)
 {
     return with_depth<TB_MAXT>(T, [](auto t) -> KernelRef<AdjTBArgs> { return {k_adj_tb<t()>, 64 * TB_NW}; });
+}
+KernelRef<BornTBArgs> born_tb_kernel(int T, bool gen)
+{
+    return with_depth<TB_MAXT>(T, [&](auto t) -> KernelRef<BornTBArgs> {
+        return {gen ? k_born_tb<t(), true> : k_born_tb<t(), false>, 64 * TB_NW};
+    });
 }
 
 // wide chunked regions: forward 16 waves x 8 rows (128 x 128), adjoint 16 waves x 4 rows (128 x 64:
@@ -3580,17 +3843,20 @@ __global__ __launch_bounds__(256) void k_ckpt_levels(const float *src, float *ds
 //   adj_ckpt  per segment, from the last to the first: the segment buffer's levels 0 and 1 from the
 //             checkpoint (k_ckpt_levels), the fwd_hist launches of the segment (hbase = lo: the recompute,
 //             no seismograms), then its adjoint launches (dseis, wavelet and record indices stay absolute).
+//   born      the linearised forward: the launches of fwd_ring over the one-segment plan (dP ping-pongs in the
+//             ring), each also reading the stored history (hbase = 0).  Always the narrow kernels (k_born_tb) at
+//             the forward's narrow depth, whatever the plan's wide or persistent settings are.
 // The adjoint's levels stay in the ring between launches and the ring parity runs on across segments.
 // Every launch of a chain is ordered on the chain's stream, so a segment's recompute overwrites the
 // segment buffer only after the previous segment's adjoint has read it.
-enum class Pass { fwd_ring, fwd_hist, adj_hist, adj_ckpt };
+enum class Pass { fwd_ring, fwd_hist, adj_hist, adj_ckpt, born };
 enum class Store { none, ring, ckpt, hist };
 struct LevelPair {                   // two consecutive levels {slot, slot + 1} of a store (none: nullptr)
     Store store;
     int slot;
 };
 struct Launch {
-    enum Kind { levels, fwd, adj } kind;
+    enum Kind { levels, fwd, adj, born } kind;
     int chain, s_off, ns_sh;         // launch chain and its shots [s_off, s_off + ns_sh) of every model
     int first, nsteps;               // fwd: steps first, first + 1, ...; adj: steps first, first - 1, ...
     int seg, hbase;                  // segment, and the slot held by the history buffer's first level
@@ -3601,22 +3867,23 @@ struct Launch {
 
 std::vector<Launch> chunked_schedule(const rdq_fwi_plan *p, int B, Pass pass, const CkptPlan &cp)
 {
-    const int Tf = chunk_depth(p, false), Ta = chunk_depth(p, true), S = chain_count(p), ns = p->g.ns;
+    const bool wide = p->wide && pass != Pass::born;
+    const int Tf = wide ? wide_fwd_depth(p) : p->fwd_T, Ta = chunk_depth(p, true), S = chain_count(p, wide), ns = p->g.ns;
     std::vector<Launch> sched;
     auto add = [&](Launch::Kind kind, int c, int sg, int first, int nsteps, LevelPair in, LevelPair out) {
         Launch l{};
         l.kind = kind; l.chain = c; l.seg = sg; l.first = first; l.nsteps = nsteps; l.in = in; l.out = out;
-        l.hbase = pass == Pass::fwd_ring ? 0 : cp.lo(sg);
+        l.hbase = pass == Pass::fwd_ring || pass == Pass::born ? 0 : cp.lo(sg);
         l.s_off = c * ns / S;
         l.ns_sh = (c + 1) * ns / S - l.s_off;
         if (kind != Launch::levels) {
             // tile grid of this launch's depth (the wide kernels run a short tail as its own depth); wide
             // kernels: spw shots of one region per workgroup (the decode's slice groups are shot groups)
             const bool adj = kind == Launch::adj;
-            const int Tl = p->wide ? nsteps : (adj ? Ta : Tf);
-            l.tiles_x = p->wide ? tw_tiles_x(p->Wp, Tl) : tiles_x(p->Wp, Tl);
-            l.ntiles = l.tiles_x * (p->wide ? tw_tiles_y(p->Hp, Tl, adj) : tiles_y(p->Hp, Tl));
-            l.spw = p->wide ? wide_spw(adj ? p->adj_spw : p->fwd_spw, B * l.ntiles, l.ns_sh, adj, S) : 1;
+            const int Tl = wide ? nsteps : (adj ? Ta : Tf);
+            l.tiles_x = wide ? tw_tiles_x(p->Wp, Tl) : tiles_x(p->Wp, Tl);
+            l.ntiles = l.tiles_x * (wide ? tw_tiles_y(p->Hp, Tl, adj) : tiles_y(p->Hp, Tl));
+            l.spw = wide ? wide_spw(adj ? p->adj_spw : p->fwd_spw, B * l.ntiles, l.ns_sh, adj, S) : 1;
             l.ns_grp = (l.ns_sh + l.spw - 1) / l.spw;
             l.grid = (unsigned)((l.ntiles + 7) / 8 * 8 * B * l.ns_grp);
         }
@@ -3624,12 +3891,13 @@ std::vector<Launch> chunked_schedule(const rdq_fwi_plan *p, int B, Pass pass, co
     };
     for (int c = 0; c < S; ++c) {
         int i = 0;                                               // ring parity: runs on across segments
-        if (pass == Pass::fwd_ring) {
+        if (pass == Pass::fwd_ring || pass == Pass::born) {
+            const Launch::Kind kind = pass == Pass::born ? Launch::born : Launch::fwd;
             for (int sg = cp.nseg - 1; sg >= 0; --sg) {
                 const int lo = cp.lo(sg), hi = cp.hi(sg);
                 for (int n0 = lo; n0 < hi; n0 += Tf, ++i) {
                     const int n = std::min(Tf, hi - n0), pin = i & 1, pout = pin ^ 1;
-                    add(Launch::fwd, c, sg, n0, n,
+                    add(kind, c, sg, n0, n,
                         n0 == lo && lo > 0 ? LevelPair{Store::ckpt, 2 * sg} : LevelPair{Store::ring, 2 * pin},
                         n0 + n == hi && hi < cp.nt ? LevelPair{Store::ckpt, 2 * (sg - 1)} : LevelPair{Store::ring, 2 * pout});
                 }                                                // (checkpoint sg = pair sg - 1 of the store)
@@ -3673,6 +3941,7 @@ struct ChunkBufs {
     float *gA;
     double *gk;
     float *gbeta;
+    const float *dwork;              // born: the perturbation workspace (`seis` is then the linearised record)
 };
 
 int enqueue_chunked(rdq_fwi_plan *p, int B, Pass pass, int K, const ChunkBufs &b, hipStream_t st)
@@ -3680,9 +3949,10 @@ int enqueue_chunked(rdq_fwi_plan *p, int B, Pass pass, int K, const ChunkBufs &b
     const std::vector<Launch> sched = chunked_schedule(p, B, pass, ckpt_plan(p, K));
     FwdTBArgs f{};
     AdjTBArgs a{};
-    f.g = a.g = tb_geo(p, B);
+    BornTBArgs d{};
+    f.g = a.g = d.g = tb_geo(p, B);
     const size_t L = a.g.level, slice = a.g.slice;
-    const int S = chain_count(p), ns = p->g.ns, nblk_alloc = gk_blocks(p);
+    const int S = chain_count(p, p->wide && pass != Pass::born), ns = p->g.ns, nblk_alloc = gk_blocks(p);
     const bool adjoint = pass == Pass::adj_hist || pass == Pass::adj_ckpt;
     if (adjoint) {   // the gk_part one-writer invariant, on every adjoint launch, before anything is enqueued
         GkWriters writers((size_t)B * ns, nblk_alloc);
@@ -3698,8 +3968,13 @@ int enqueue_chunked(rdq_fwi_plan *p, int B, Pass pass, int K, const ChunkBufs &b
                               {b.gbeta, (size_t)B * ns * sizeof(float)}}, st));
     else if (pass == Pass::fwd_hist) RDQ_TRY(zero_regions({{b.hist, 2 * L * sizeof(float)}}, st));
     else RDQ_TRY(zero_regions({{b.ring, 4 * L * sizeof(float)}}, st));
-    f.coeffs = a.coeffs = b.coeffs;
-    f.cg = a.cg = coef_gen(p, B, b.coeffs);
+    f.coeffs = a.coeffs = d.coeffs = b.coeffs;
+    f.cg = a.cg = d.cg = coef_gen(p, B, b.coeffs);
+    d.hist = b.hist; d.dseis = b.seis;
+    d.dam = b.dwork;
+    d.ratio = b.dwork ? b.dwork + (size_t)B * p->g.nz * p->g.nx : nullptr;
+    d.dbeta = b.dwork ? d.ratio + B : nullptr;
+    d.oscale = b.dwork ? d.dbeta + (size_t)B * p->g.ns : nullptr;
     f.seis = b.seis; f.hist = b.hist;
     a.hist = b.hist; a.dseis = b.dseis; a.gA = b.gA; a.gk_part = b.gk; a.gbeta = b.gbeta;
     a.nblk = nblk_alloc;
@@ -3724,6 +3999,13 @@ int enqueue_chunked(rdq_fwi_plan *p, int B, Pass pass, int K, const ChunkBufs &b
             f.in_prev = level(l.in, 0); f.in_cur = level(l.in, 1);
             f.out_prev = level(l.out, 0); f.out_cur = level(l.out, 1);
             launch_kernel(chunk_fwd_kernel(p, l.nsteps), l.grid, cs, f);
+        } else if (l.kind == Launch::born) {
+            d.g.s_off = l.s_off; d.g.ns_grp = l.ns_grp; d.g.tiles_x = l.tiles_x; d.g.ntiles = l.ntiles;
+            d.n0 = l.first; d.nsteps = l.nsteps;
+            for (int t = 0; t < TB_MAXT; ++t) d.w[t] = t < l.nsteps ? p->wavf[l.first + t] : 0.0f;
+            d.in_prev = level(l.in, 0); d.in_cur = level(l.in, 1);
+            d.out_prev = level(l.out, 0); d.out_cur = level(l.out, 1);
+            launch_kernel(born_tb_kernel(p->fwd_T, p->fwd_gen), l.grid, cs, d);
         } else {
             a.g.s_off = l.s_off; a.g.ns_grp = l.ns_grp; a.g.tiles_x = l.tiles_x; a.g.ntiles = l.ntiles;
             a.ns_sh = l.ns_sh; a.spw = l.spw;
@@ -4264,6 +4546,53 @@ int rdq_fwi_adjoint(const rdq_fwi_plan *pc, int32_t B, const float *coeffs, cons
     b.gA = gA; b.gk = gk; b.gbeta = gbeta;
     return run_cached(p, 2, B, {coeffs, hist, dseis, ring, gA, gk, gbeta}, st,
                       [&](hipStream_t s) { return enqueue_chunked(p, B, Pass::adj_hist, p->g.nt, b, s); });
+}
+
+// perturbation workspace: dam [B][nz][nx], ratio [B], dbeta [B][ns], oscale [B], dmax [B] (k_dcoeffs)
+int rdq_fwi_born_sizes(const rdq_fwi_plan *p, int32_t B, size_t *bytes)
+{
+    if (!p || !bytes || B < 1) return RDQ_E_INVALID;
+    *bytes = ((size_t)B * p->g.nz * p->g.nx + 3 * (size_t)B + (size_t)B * p->g.ns + 4) * sizeof(float);
+    return 0;
+}
+
+int rdq_fwi_dcoeffs(const rdq_fwi_plan *p, int32_t B, const float *dv, const int64_t strides[4], int32_t vel_mode,
+                    const float *coeffs, const void *vstat, float *dwork, hipStream_t st)
+{
+    if (!p || !dv || !strides || !coeffs || !vstat || !dwork || B < 1 || (vel_mode != 0 && vel_mode != 1))
+        return RDQ_E_INVALID;
+    float *vmin; int64_t *amin;
+    vstat_ptrs(vstat, B, &vmin, &amin);
+    DCoefArgs a;
+    a.dv = dv; a.s0 = strides[0]; a.s2 = strides[2]; a.s3 = strides[3];
+    a.vel_mode = vel_mode; a.B = B; a.nz = p->g.nz; a.nx = p->g.nx; a.ns = p->g.ns; a.nbc = p->g.nbc;
+    a.isz = p->g.isz; a.ld = p->ld; a.dt = p->g.dt; a.dx = p->g.dx;
+    a.slice = (size_t)p->Hp * p->ld; a.cstride = (size_t)B * a.slice;
+    a.coeffs = coeffs; a.vmod = coef_gen(p, B, coeffs).vmod; a.vmin = vmin; a.amin = amin; a.isx = p->d_isx;
+    a.dam = dwork; a.ratio = dwork + (size_t)B * p->g.nz * p->g.nx; a.dbeta = a.ratio + B;
+    a.oscale = a.dbeta + (size_t)B * p->g.ns;
+    a.dmax = reinterpret_cast<unsigned *>(a.oscale + B);
+    const size_t n = (size_t)B * p->g.nz * p->g.nx + (size_t)B + (size_t)B * p->g.ns;
+    if (n > 0x7fffffffu) return RDQ_E_INVALID;
+    RDQ_TRY(zero_regions({{a.dmax, (size_t)B * sizeof(unsigned)}}, st));
+    const int cells = p->g.nz * p->g.nx;
+    hipLaunchKernelGGL(k_dmax, dim3((unsigned)std::max(1, std::min(64, (cells + 2047) / 2048)), B), dim3(256), 0, st, a);
+    hipLaunchKernelGGL(k_dcoeffs, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, st, a);
+    RDQ_CHECK(hipGetLastError());
+    return 0;
+}
+
+int rdq_fwi_born(const rdq_fwi_plan *pc, int32_t B, const float *coeffs, const float *dwork, const float *hist,
+                 float *dseis, float *ring, hipStream_t st)
+{
+    rdq_fwi_plan *p = const_cast<rdq_fwi_plan *>(pc);
+    if (!p || !coeffs || !dwork || !hist || !dseis || !ring || B < 1) return RDQ_E_INVALID;
+    std::lock_guard<std::mutex> lk(p->mu);
+    RDQ_TRY(plan_enter(p, st));
+    ChunkBufs b{};
+    b.coeffs = coeffs; b.dwork = dwork; b.hist = const_cast<float *>(hist); b.seis = dseis; b.ring = ring;
+    return run_cached(p, 5, B, {coeffs, dwork, hist, dseis, ring}, st,
+                      [&](hipStream_t s) { return enqueue_chunked(p, B, Pass::born, p->g.nt, b, s); });
 }
 
 int rdq_fwi_ckpt_sizes(const rdq_fwi_plan *p, int32_t B, int32_t K, rdq_fwi_ckpt_sizes_t *o)

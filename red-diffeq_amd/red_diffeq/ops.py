@@ -14,6 +14,8 @@ torch.compile see them as ordinary operators instead of opaque ctypes calls.
     red_diffeq::fwi_grad_finalize(coeffs, vstat, gA, gk, gbeta, plan, B, vel_mode) -> grad   K4
     red_diffeq::fwi(v, plan, vel_mode, keep_history) -> (seis, coeffs, vstat, history)
         differentiable in v (register_autograd: adjoint + finalize), what FWIForward calls
+    red_diffeq::fwi_born(coeffs, vstat, history, dv, plan, B, vel_mode) -> dseis
+        the linearised forward J dv over a stored history (FWIForward.born / gauss_newton; no autograd formula)
     red_diffeq::fwi_forward_ckpt(coeffs, plan, B, K) -> (seis, ckpt)               K1, checkpoints every K steps
     red_diffeq::fwi_adjoint_ckpt(coeffs, ckpt, seg, dseis, plan, B, K) -> (gA, gk, gbeta)
         K2 over segments recomputed into the scratch `seg` (the one mutated argument)
@@ -209,6 +211,35 @@ def _fwi_backward(ctx, gseis, _gc, _gv, _gh):
 
 
 fwi.register_autograd(_fwi_backward, setup_context=_fwi_setup)
+
+
+# ---- linearised (Born) forward: J dv over the stored history (rdq_fwi_dcoeffs + rdq_fwi_born)
+@torch.library.custom_op(f"{LIB}::fwi_born", mutates_args=())
+def fwi_born(coeffs: Tensor, vstat: Tensor, history: Tensor, dv: Tensor, plan: int, B: int, vel_mode: int) -> Tensor:
+    """dseis = J dv at the model `coeffs` / `vstat` / `history` (fwi_coeffs, fwi_forward with history) belong to."""
+    p = _plan(plan)
+    _hip.require_device(coeffs, vstat, history, dv)
+    sz = p.sizes(B)
+    if tuple(dv.shape) != (B, 1, p.nz, p.nx) or history.numel() * 4 != sz.history:
+        raise ValueError("fwi_born: dv / history do not match the plan")
+    dv = dv.float()
+    nbytes = ctypes.c_size_t()
+    _hip.check(p.lib.rdq_fwi_born_sizes(p.handle, B, ctypes.byref(nbytes)), "rdq_fwi_born_sizes")
+    dwork = _f32(nbytes.value, coeffs.device)
+    ring = _f32(sz.ring, coeffs.device)
+    dseis = torch.empty(_seis_shape(p, B), dtype=torch.float32, device=coeffs.device)
+    strides = (ctypes.c_int64 * 4)(*dv.stride())
+    st = _hip.stream_of(coeffs)
+    _hip.check(p.lib.rdq_fwi_dcoeffs(p.handle, B, _hip.ptr(dv), strides, vel_mode, _hip.ptr(coeffs), _hip.ptr(vstat),
+                                     _hip.ptr(dwork), st), "rdq_fwi_dcoeffs")
+    _hip.check(p.lib.rdq_fwi_born(p.handle, B, _hip.ptr(coeffs), _hip.ptr(dwork), _hip.ptr(history), _hip.ptr(dseis),
+                                  _hip.ptr(ring), st), "rdq_fwi_born")
+    return dseis
+
+
+@fwi_born.register_fake
+def _(coeffs, vstat, history, dv, plan, B, vel_mode):
+    return coeffs.new_empty(_seis_shape(_plan(plan), B))
 
 
 # ---- checkpointed gradient: the history bounded by recomputation (rdq_fwi_forward_ckpt / _adjoint_ckpt)

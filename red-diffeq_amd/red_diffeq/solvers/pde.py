@@ -22,7 +22,7 @@ import torch.nn.functional as F
 
 from .. import _hip
 from .. import ops as _ops   # registers torch.ops.red_diffeq.*
-from ..utils.data_trans import v_denormalize
+from ..utils.data_trans import s_normalize_none, v_denormalize
 
 
 def ricker(f, dt, nt):
@@ -282,6 +282,12 @@ class FwiPlan:
     def finalize(self, coeffs, vstat, gA, gk, gb, B, vel_mode):
         return torch.ops.red_diffeq.fwi_grad_finalize(coeffs, vstat, gA, gk, gb, self.op_id, B, vel_mode)
 
+    def born(self, coeffs, vstat, hist, dv, B, vel_mode):
+        """J dv (the seismograms' shape) over the store-all history `hist` of forward(coeffs, B, True): the
+        narrow chunked Born kernels at set_tuning's forward depth and chains, whatever the persistent / wide
+        settings are; bit-identical for every depth, chain count and graph setting."""
+        return torch.ops.red_diffeq.fwi_born(coeffs, vstat, hist, dv, self.op_id, int(B), int(vel_mode))
+
     # ---- checkpointed gradient (rdq_fwi_*_ckpt): history bounded by recomputation ----
     def ckpt_sizes(self, B, K):
         """rdq_fwi_ckpt_sizes_t of a checkpointed gradient with K steps per segment: .nseg, .seg_levels,
@@ -455,6 +461,72 @@ class FWIForward(nn.Module):
         else:
             s = torch.ops.red_diffeq.fwi(v, plan.op_id, vel_mode, keep)[0]   # backward: K2 + K4 (ops.py)
         return self.s_norm_func(s) if self.normalize else s
+
+    # --- linearisation: J dv and the Gauss-Newton product ---------------------------------------
+    def _linearise(self, v, dv, what):
+        """Checks (before any device work), then the model, the direction and vel_mode as K3 takes them, and
+        the pull-back of a model gradient through a custom denormalisation (None when it is fused)."""
+        if v.dim() != 4 or v.shape[1] != 1:
+            raise ValueError(f"{what}: expected v of shape (B,1,H,W), got {tuple(v.shape)}")
+        if tuple(dv.shape) != tuple(v.shape):
+            raise ValueError(f"{what}: dv has shape {tuple(dv.shape)}, v {tuple(v.shape)}")
+        _hip.require_device(v, dv)
+        v, dv = v.detach().float(), dv.detach().float()
+        if self._fused_denorm():
+            return v, dv, 0, None
+        if not self.normalize:
+            return v, dv, 1, None
+        vn = v                                   # an arbitrary callable: its tangent and transpose through torch
+        v, dv = torch.func.jvp(self.v_denorm_func, (vn,), (dv,))
+        return v, dv, 1, lambda g: torch.func.vjp(self.v_denorm_func, vn)[1](g)[0]
+
+    def _born(self, v, dv, vel_mode):
+        """K3, the forward with its store-all history, the Born prologue and time loop."""
+        plan = self._plan(v.shape[2], v.shape[3], v.device)
+        self._last = plan
+        B = v.shape[0]
+        need = int(plan.sizes(B).history)
+        if self.history_budget_gb is not None and need > int(float(self.history_budget_gb) * 2 ** 30):
+            raise ValueError(f"born / gauss_newton keep a store-all history of {need} bytes, more than "
+                             f"history_budget_gb = {self.history_budget_gb}; a checkpointed Born pass does not exist")
+        coeffs, vstat = plan.coeffs(v, vel_mode)
+        seis, hist = plan.forward(coeffs, B, True)
+        return plan, coeffs, vstat, hist, seis, plan.born(coeffs, vstat, hist, dv, B, vel_mode)
+
+    def _custom_s_norm(self):
+        return self.normalize and self.s_norm_func is not s_normalize_none
+
+    def born(self, v, dv, return_seis=False):
+        """Linearised (Born) modelling: J dv, J = d forward(v) / d v, with the shape of forward(v); with
+        return_seis, (forward(v), J dv).  Runs under no_grad on a store-all history (ValueError with the byte
+        count when history_budget_gb is set and it does not fit); the result does not require grad.  A custom
+        v_denorm_func, and an s_norm_func other than s_normalize_none, are chained with torch.func.jvp.  With
+        shots=, this rank's shots only, as forward."""
+        v, dv, vel_mode, _ = self._linearise(v, dv, "born")
+        with torch.no_grad():
+            seis, ds = self._born(v, dv, vel_mode)[4:]
+        if self._custom_s_norm():
+            seis, ds = torch.func.jvp(self.s_norm_func, (seis,), (ds,))
+        seis, ds = seis.detach(), ds.detach()
+        return (seis, ds) if return_seis else ds
+
+    def gauss_newton(self, v, dv, weight=None):
+        """The Gauss-Newton product J^T (weight * J dv), with the shape of v: one forward with history, one Born
+        pass, then the adjoint and the finalize on the same history (no second forward).  Bit-equal to
+        s = forward(v); s.backward(weight * born(v, dv)); v.grad."""
+        v, dv, vel_mode, pull = self._linearise(v, dv, "gauss_newton")
+        with torch.no_grad():
+            plan, coeffs, vstat, hist, seis, ds = self._born(v, dv, vel_mode)
+        if self._custom_s_norm():
+            ds = torch.func.jvp(self.s_norm_func, (seis,), (ds,))[1]
+        r = ds if weight is None else weight * ds
+        if self._custom_s_norm():
+            r = torch.func.vjp(self.s_norm_func, seis)[1](r)[0]
+        with torch.no_grad():
+            gA, gk, gb = plan.adjoint(coeffs, hist, r.detach().contiguous(), v.shape[0])
+            del hist
+            g = plan.finalize(coeffs, vstat, gA, gk, gb, v.shape[0], vel_mode)
+        return (g if pull is None else pull(g)).detach()
 
     def checkpoint_interval(self, plan, B):
         """Steps per segment of the checkpointed gradient a differentiable call with batch B runs, or None
