@@ -318,7 +318,11 @@ int rdq_fwi_ckpt_info(rdq_fwi_plan *plan, int32_t B, int32_t K, int32_t out[4]);
  *   accumulates into gA and gk_part.
  *   Scale.  J is linear, so the prologue brings each model's direction to a fixed magnitude with a power of two
  *   (dvs = dv 2^-k, max |dvs| in [2^-64, 2^-63)) and the time loop multiplies what it records by 2^k: the loop runs
- *   on the same bits whatever the magnitude of dv, and for max |dv| >= 2^-64 the rescale is exact.
+ *   on the same bits whatever the magnitude of dv, and for max |dv| >= 2^-64 the rescale is exact.  k = floor(log2
+ *   max |dv|) + 64, kept within [-63, 126] so that 2^k and 2^-k are normal floats: for max |dv| >= 2^63 the scale
+ *   stays at 2^-126 and max |dvs| grows with the direction (2 at the largest float: still an exact rescale, far
+ *   from overflow), and for max |dv| below the smallest normal float (denormals, or a zero direction) the scale is
+ *   2^63 and max |dvs| < 2^-63.
  *   Layout.  `dwork` (rdq_fwi_born_sizes bytes) is float dam [B][nz][nx] (dA per model cell, from dvs in m/s; a
  *   padded cell reads the model cell its clamped index names), then ratio [B] (dvs[argmin] / vmin), dbeta [B][ns],
  *   oscale [B] (2^k) and uint32 dmax [B] (the bits of max |dv|);

@@ -784,6 +784,10 @@ __global__ __launch_bounds__(64 * TB_NW, 4) void k_adj_tb(AdjTBArgs a)
 // 2^j J dv bit for bit.  (Without it the equality breaks wherever the tangent field is near the underflow
 // threshold: measured at the 88 x 118 test grid, 1575 of 23040 recorded values, all below 1e-13 of the record's
 // peak.)  2^-64 leaves the loop 85 binades between a unit response and the smallest denormal; fp32 resolves 24.
+// The fixed magnitude holds for 2^-126 <= max |dv| < 2^63.  k = floor(log2 max |dv|) + 64 is kept within [-63, 126],
+// where 2^k and 2^-k are normal floats (dcoef_exp): for max |dv| >= 2^63 the scale stays at 2^-126 and max |dvs| grows
+// with the direction (2 at the largest float: an exact rescale still, far from overflow); for a max |dv| below the
+// smallest normal float (biased exponent 0: denormals, or a zero direction) the scale is 2^63 and max |dvs| < 2^-63.
 //
 // Perturbation workspace (rdq_fwi_born_sizes; written by the prologue, k_dmax + k_dcoeffs):
 //   dam    [B][nz][nx]  dA per model cell, (2 (v dt / dx)) ((dvs dt) / dx) with dvs in m/s (x1500 of a normalised
@@ -828,7 +832,8 @@ __global__ __launch_bounds__(256) void k_dmax(DCoefArgs p)
     if (threadIdx.x == 0) atomicMax(&p.dmax[b], sm[0]);
 }
 
-// biased exponent of max |dv|, kept where both powers of two below are normal floats
+// biased exponent of max |dv|, kept where both powers of two below are normal floats: 0 (max |dv| denormal or zero)
+// gives the scale 2^63, 189 and above (max |dv| >= 2^63) the scale 2^-126
 __device__ __forceinline__ unsigned dcoef_exp(const DCoefArgs &p, int b) { return min(p.dmax[b] >> 23, 189u); }
 
 __device__ __forceinline__ float dcoef_dv(const DCoefArgs &p, int b, int iz, int ix)

@@ -2,7 +2,8 @@
 """Generate tests/golden/born.npz: the REFERENCE's FWIForward (solvers/pde.py) linearised on the CPU with
 torch.func.jvp, in fp64 and in fp32, and its fp64 autograd adjoint, for FWIForward.born / gauss_newton.
 
-Run:  python tests/golden/make_born.py
+Run:  python tests/golden/make_born.py          writes born.npz
+      python tests/golden/make_born.py terms    writes born_terms.npz (below) and leaves born.npz alone
 
 Cases (nt = 160, dt = 1e-3, f = 15: a 147-sample wavelet; dx = 10), the smallest shapes at which the Born
 kernel can go wrong:
@@ -27,6 +28,22 @@ Per case <tag>:
   <tag>_ip                                  (<J dv, w>, <dv, J^T w>) in fp64
 Asserted here in fp64: the jvp agrees with a central difference (h = 1e-3) to 1e-6, the two inner products
 agree to 1e-10, every E_ref > 0.
+
+born_terms.npz, one case `terms`: the tangent has four sources (dA in the model, dA replicated into the pad, dK =
+K dv[argmin] / vmin in the sponge, dbeta at the source cells) and a dense direction lets the interior dA drown
+the other three.  Here every direction is 0.04 at ONE cell per model and zero elsewhere.
+  nz 20, nx 30, nbc 24 (padded 68 x 78: two tile rows and two tile columns at depth 4), 3 shots (source cells
+  (1, 0), (1, 14), (1, 29)), 7 receivers, sz = gz = 10, B = 2, normalised; model 0 has its unique minimum at
+  (11, 6), model 1 at the corner (0, 0).
+  direction   model 0    model 1    isolates
+  argmin      (11, 6)    (0, 0)     dK through the sponge, plus the corner's replicated dA for model 1
+  source      (1, 14)    (1, 14)    dbeta
+  corner      (19, 29)   (19, 29)   dA replicated into an nbc x nbc pad block
+  edge        (0, 17)    (12, 0)    dA replicated into a pad strip, top and left
+  interior    (10, 20)   (10, 20)   a single interior dA cell, the baseline
+  terms_ctx_*, terms_normalize, terms_st, terms_v, terms_w, terms_jtw64      once, as above
+  terms_<direction>_dv / _jdv64 / _jdv32 / _eref / _ip                       per direction, as above
+with the same assertions per direction.
 """
 import copy
 import os
@@ -53,13 +70,15 @@ def rel_l2(a, b):
     return float((a - b).norm() / b.norm())
 
 
-def run_case(tag, ctx, normalize, st, v, dv, seed, out):
-    fw = operator(ctx, normalize, st)
-    v32, dv32 = torch.from_numpy(v), torch.from_numpy(dv)
-    v64, dv64 = v32.double(), dv32.double()
+def unique_minimum(tag, v64):
     flat = v64.flatten(1)
-    for b in range(v.shape[0]):                                    # a unique minimum per model
+    for b in range(v64.shape[0]):
         assert int((flat[b] == flat[b].min()).sum()) == 1, (tag, b)
+
+
+def linearise(tag, fw, v32, dv32):
+    """(forward, J dv) in fp64, J dv in fp32, E_ref per model and the jvp's distance from a central difference."""
+    v64, dv64 = v32.double(), dv32.double()
     seis64, jdv64 = torch.func.jvp(fw, (v64,), (dv64,))
     assert seis64.dtype == torch.float64
     _, jdv32 = torch.func.jvp(fw, (v32,), (dv32,))
@@ -68,22 +87,35 @@ def run_case(tag, ctx, normalize, st, v, dv, seed, out):
     with torch.no_grad():
         cd = (fw(v64 + h * dv64) - fw(v64 - h * dv64)) / (2 * h)
     assert rel_l2(cd, jdv64) < 1e-6, (tag, rel_l2(cd, jdv64))
-    w32 = torch.randn(seis64.shape, generator=torch.Generator().manual_seed(seed))
-    w64 = w32.double()
+    eref = np.array([rel_l2(jdv32[b].double(), jdv64[b]) for b in range(v32.shape[0])])
+    assert (eref > 0).all(), (tag, eref)
+    return seis64, jdv64, jdv32, eref, rel_l2(cd, jdv64)
+
+
+def adjoint(fw, v64, w64):
     vg = v64.clone().requires_grad_(True)
     (fw(vg) * w64).sum().backward()
-    jtw64 = vg.grad
+    return vg.grad
+
+
+def run_case(tag, ctx, normalize, st, v, dv, seed, out):
+    fw = operator(ctx, normalize, st)
+    v32, dv32 = torch.from_numpy(v), torch.from_numpy(dv)
+    v64, dv64 = v32.double(), dv32.double()
+    unique_minimum(tag, v64)                                       # a unique minimum per model
+    seis64, jdv64, jdv32, eref, cderr = linearise(tag, fw, v32, dv32)
+    w32 = torch.randn(seis64.shape, generator=torch.Generator().manual_seed(seed))
+    w64 = w32.double()
+    jtw64 = adjoint(fw, v64, w64)
     lhs, rhs = float((jdv64 * w64).sum()), float((dv64 * jtw64).sum())
     assert abs(lhs - rhs) <= 1e-10 * max(abs(lhs), abs(rhs)), (tag, lhs, rhs)
-    eref = np.array([rel_l2(jdv32[b].double(), jdv64[b]) for b in range(v.shape[0])])
-    assert (eref > 0).all(), (tag, eref)
     out.update({f"{tag}_ctx_{k}": np.asarray(x) for k, x in ctx.items()})
     out.update({f"{tag}_normalize": np.array(normalize), f"{tag}_st": np.array(st), f"{tag}_v": v, f"{tag}_dv": dv,
                 f"{tag}_w": w32.numpy(), f"{tag}_seis64": seis64.numpy(), f"{tag}_jdv64": jdv64.numpy(),
                 f"{tag}_jtw64": jtw64.numpy(), f"{tag}_jdv32": jdv32.numpy(), f"{tag}_eref": eref,
                 f"{tag}_ip": np.array([lhs, rhs])})
     print(f"{tag}: seis {tuple(seis64.shape)}, E_ref {eref}, <Jdv,w> {lhs:.15e}, <dv,JTw> {rhs:.15e}, "
-          f"jvp vs central difference {rel_l2(cd, jdv64):.2e}")
+          f"jvp vs central difference {cderr:.2e}")
 
 
 def model(kind, nz, nx, seed, batch, argmins, normalised):
@@ -127,5 +159,48 @@ def main():
     assert os.path.getsize(os.path.join(HERE, "born.npz")) <= 1 << 20
 
 
+TERMS = {"argmin": ((11, 6), (0, 0)), "source": ((1, 14), (1, 14)), "corner": ((19, 29), (19, 29)),
+         "edge": ((0, 17), (12, 0)), "interior": ((10, 20), (10, 20))}
+
+
+def main_terms():
+    torch.set_num_threads(8)
+    ctx = dict(BASE, n_grid=30, nbc=24, sz=10, gz=10, ng=7, ns=3)
+    v = model("curvevel", 20, 30, 51, 2, [(11, 6), (0, 0)], True)
+    fw = operator(ctx, True, 1)
+    isx, isz = fw.adj_sr(fw.ctx["sx"], ctx["sz"], fw.ctx["gx"], ctx["gz"], ctx["dx"], ctx["nbc"])[:2]
+    assert isz - ctx["nbc"] == 1 and list(isx - ctx["nbc"]) == [0, 14, 29], (isz, isx)
+    v32 = torch.from_numpy(v)
+    v64 = v32.double()
+    unique_minimum("terms", v64)
+    assert [divmod(int(v64[b].argmin()), 30) for b in range(2)] == [(11, 6), (0, 0)]
+    out = {f"terms_ctx_{k}": np.asarray(x) for k, x in ctx.items()}
+    w32 = None
+    for name, cells in TERMS.items():
+        dv = np.zeros_like(v)
+        for b, (iz, ix) in enumerate(cells):
+            dv[b, 0, iz, ix] = 0.04
+        dv32 = torch.from_numpy(dv)
+        seis64, jdv64, jdv32, eref, cderr = linearise(name, fw, v32, dv32)
+        if w32 is None:
+            w32 = torch.randn(seis64.shape, generator=torch.Generator().manual_seed(53))
+            jtw64 = adjoint(fw, v64, w32.double())
+        lhs, rhs = float((jdv64 * w32.double()).sum()), float((dv32.double() * jtw64).sum())
+        assert abs(lhs - rhs) <= 1e-10 * max(abs(lhs), abs(rhs)), (name, lhs, rhs)
+        out.update({f"terms_{name}_dv": dv, f"terms_{name}_jdv64": jdv64.numpy(), f"terms_{name}_jdv32": jdv32.numpy(),
+                    f"terms_{name}_eref": eref, f"terms_{name}_ip": np.array([lhs, rhs])})
+        print(f"terms/{name}: record {tuple(jdv64.shape)}, E_ref {eref}, <Jdv,w> {lhs:.15e}, <dv,JTw> {rhs:.15e}, "
+              f"jvp vs central difference {cderr:.2e}, max |J dv| / max |dv| {float(jdv64.abs().max()) / 0.04:.3e}")
+    out.update({"terms_normalize": np.array(True), "terms_st": np.array(1), "terms_v": v, "terms_w": w32.numpy(),
+                "terms_jtw64": jtw64.numpy()})
+    G.save("born_terms", **out)
+    assert os.path.getsize(os.path.join(HERE, "born_terms.npz")) <= 1 << 20
+
+
 if __name__ == "__main__":
-    main()
+    if sys.argv[1:] == ["terms"]:
+        main_terms()
+    elif sys.argv[1:]:
+        sys.exit(f"usage: {sys.argv[0]} [terms]")
+    else:
+        main()
