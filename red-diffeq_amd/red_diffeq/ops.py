@@ -1171,8 +1171,10 @@ def l1_misfit_backward(pred: Tensor, y: Tensor, mask: Optional[Tensor], nobs: Te
     mask = mask.float().contiguous() if mask is not None else None
     B = pred.shape[0]
     dpred = torch.empty_like(pred)
+    # named, so that the copy of an expanded (stride-0) gout lives until the launch is enqueued
+    nobs, gout = nobs.float().contiguous(), gout.float().contiguous()
     _hip.check(_hip.lib().rdq_l1_backward(B, pred.numel() // B, _hip.ptr(pred), _hip.ptr(y), _hip.ptr(mask),
-                                          _hip.ptr(nobs.float().contiguous()), _hip.ptr(gout.float().contiguous()),
+                                          _hip.ptr(nobs), _hip.ptr(gout),
                                           _hip.ptr(dpred), _hip.stream_of(pred)), "rdq_l1_backward")
     return dpred
 
@@ -1205,7 +1207,8 @@ def smooth_reg_backward(mu: Tensor, gout: Tensor, kind: int) -> Tensor:
     m = mu.float().contiguous()
     B, _, H, W = m.shape
     grad = torch.empty_like(m)
-    _hip.check(_hip.lib().rdq_smooth_reg_backward(kind, B, H, W, _hip.ptr(m), _hip.ptr(gout.float().contiguous()),
+    gout = gout.float().contiguous()   # named: the copy of an expanded gout lives until the launch is enqueued
+    _hip.check(_hip.lib().rdq_smooth_reg_backward(kind, B, H, W, _hip.ptr(m), _hip.ptr(gout),
                                                   _hip.ptr(grad), _hip.stream_of(m)), "rdq_smooth_reg_backward")
     return grad
 
