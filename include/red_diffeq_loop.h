@@ -27,6 +27,7 @@ extern "C" {
  *   p = p + step_size * m / (sqrt(v) / bc2_sqrt + eps)
  * step_size = -lr / (1 - beta1^t) and bc2_sqrt = sqrt(1 - beta2^t) are computed by the caller in
  * double precision exactly as torch.optim.Adam does (torch/optim/adam.py, _multi_tensor_adam).
+ * A NaN or infinite gradient leaves p NaN, clamped or not, as Adam.step() + clamp_ do.
  * guard (nullable, device): when *guard != 0 the step leaves param / exp_avg / exp_avg_sq untouched
  * (the FWI status word: a gradient from a failed persistent launch is never applied). */
 int rdq_adam_step(int64_t n, float *param, const float *grad, float *exp_avg, float *exp_avg_sq, float beta1,

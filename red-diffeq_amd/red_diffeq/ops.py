@@ -1221,7 +1221,15 @@ def _(mu, gout, kind):
 @torch.library.custom_op(f"{LIB}::metrics", mutates_args=())
 def metrics(pred: Tensor, true_norm: Tensor) -> Tensor:
     """K12: (mae, rmse, ssim) per model as a (3, B) device tensor (metrics.py:13-46)."""
-    _hip.require_device(pred)
+    _hip.require_device(pred, true_norm)
+    if pred.dtype != torch.float32 or true_norm.dtype != torch.float32:
+        raise ValueError("metrics: pred and true_norm must be fp32")
+    if pred.dim() != 4 or pred.shape[1] != 1:
+        raise ValueError("metrics: pred must be (B, 1, H, W)")
+    if true_norm.device != pred.device:
+        raise ValueError("metrics: pred and true_norm must be on the same device")
+    if true_norm.numel() != pred.numel():
+        raise ValueError("metrics: true_norm must have the elements of pred, (B, 1, H, W)")
     B, _, H, W = pred.shape
     t = true_norm.contiguous()
     L = _hip.lib()

@@ -1,8 +1,8 @@
 """Timing-only experiment builds of the HIP library (never shipped): apply textual edits to a copy of
-csrc/fwi.hip (or, with --src unet, csrc/unet.hip) and link it with the other current objects into
+csrc/fwi.hip (or, with --src unet / --src loop, csrc/unet.hip / csrc/loop.hip) and link it with the other current objects into
 red-diffeq_amd/lib_exp/lib<name>.so; select one at run time with RDQ_HIP_LIB.  The product source stays
 unchanged.
-python tools/exp_build.py [--src fwi|unet] <name> '<old>' '<new>' ['<old>' '<new>' ...]"""
+python tools/exp_build.py [--src fwi|unet|loop] <name> '<old>' '<new>' ['<old>' '<new>' ...]"""
 import os
 import subprocess
 import sys
