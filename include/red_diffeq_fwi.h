@@ -344,6 +344,31 @@ int rdq_fwi_dcoeffs(const rdq_fwi_plan *plan, int32_t B, const float *dv, const 
 int rdq_fwi_born(const rdq_fwi_plan *plan, int32_t B, const float *coeffs, const float *dwork,
                  const float *history, float *dseis_out, float *ring, hipStream_t stream);
 
+/* Fused forward + Born pass: seis and dseis = J dv in ONE time loop that keeps no wavefield history, for jobs whose
+ * store-all history does not fit (rdq_fwi_born needs all nt + 2 levels).  Forward-mode linearisation reads P_n and
+ * P_{n-1} only, and the forward step of the same register region produces exactly those levels on exactly the
+ * cells the tangent's taps read, so the kernel carries two levels of P and two of dP per launch, in and out.
+ *   Equations.  The forward step and its tangent as written above (rdq_fwi_born); `dwork` is what rdq_fwi_dcoeffs
+ *   writes, unchanged.
+ *   Layout.  `seis` and `dseis_out` are float [B][ns][nrec][ng].  `ring` as for rdq_fwi_forward: its levels 0-3
+ *   carry the P pair between launches and its levels 4-7 the dP pair.  K and `ckpt` choose the checkpoint store of
+ *   rdq_fwi_forward_ckpt: with `ckpt` non-null and K < nt the launches are cut at the segment boundaries b_c =
+ *   max(nt - c K, 0) and the launch that ends on an interior boundary writes {P_{b_c - 1}, P_{b_c}} into levels
+ *   {2 (c - 1), 2 (c - 1) + 1} of `ckpt` (rdq_fwi_ckpt_sizes(K).ckpt bytes), exactly the layout and bits of
+ *   rdq_fwi_forward_ckpt's store, so rdq_fwi_adjoint_ckpt consumes it unchanged (the Gauss-Newton product under a
+ *   history budget: this call, then rdq_fwi_adjoint_ckpt on weight * dseis, then K4).  K >= nt or `ckpt` == NULL is
+ *   one segment and nothing is stored.
+ *   The call always runs the narrow chunked kernels at rdq_fwi_set_tuning's fwd_steps and chains, as rdq_fwi_born
+ *   does, under the one-call-in-flight rule of the other time loops.  The P update is the chunked forward's
+ *   operation order and the dP update rdq_fwi_born's (no contraction; written next to the kernel), and the
+ *   Laplacian of P_n is one expression that serves both.  The forward's bits are therefore the stored history's
+ *   bits: `seis` is bit-identical to rdq_fwi_forward's, `dseis_out` to rdq_fwi_born's and `ckpt` to
+ *   rdq_fwi_forward_ckpt's, for every depth, chain count, graph setting and K.  RDQ_E_INVALID for a null required
+ *   argument (all but `ckpt`), B < 1, or K < 1 with a non-null `ckpt`. */
+int rdq_fwi_born_fused(const rdq_fwi_plan *plan, int32_t B, int32_t K, const float *coeffs,
+                       const float *dwork, float *seis, float *dseis_out, float *ckpt, float *ring,
+                       hipStream_t stream);
+
 /* K4: d(loss)/d(v) [B][nz][nx] (contiguous) from the accumulators: chain through
  * alpha/beta/sponge(vmin), replicate-pad fold, and (RDQ_VEL_NORMALIZED) the x1500 of the
  * denormalisation. */

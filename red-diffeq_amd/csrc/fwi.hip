@@ -10,6 +10,8 @@
 //   K4 rdq_fwi_grad_finalize  chain rule back to v_norm incl. the vmin/argmin sponge term
 //   -- rdq_fwi_dcoeffs / rdq_fwi_born  torch.func.jvp of pde.py:88-93 in a direction dv: the linearised (Born)
 //                          forward over K1's stored history (k_dcoeffs, k_born_tb)
+//   -- rdq_fwi_born_fused  the same jvp, primal and tangent records from one time loop that keeps no history
+//                          (k_fwd_born_tb), optionally writing the checkpoint store of rdq_fwi_forward_ckpt
 //
 // fp32 operation order follows the reference expression order exactly and the file is built
 // with -ffp-contract=off, so K1 reproduces the reference seismograms bit-for-bit and K2's
@@ -1026,6 +1028,163 @@ __global__ __launch_bounds__(64 * TB_NW) void k_born_tb(BornTBArgs a)
                 const size_t o = so + rofs[r] + gx;
                 a.out_cur[o] = odd ? D0[r] : D1[r];
                 a.out_prev[o] = odd ? D1[r] : D0[r];
+            }
+    }
+}
+
+struct FwdBornTBArgs {
+    TBGeo g;
+    CoefGen cg;                          // model + sponge amplitude (GEN variant)
+    const float *coeffs;                 // K3 fields: alpha, kappa, beta at 0, 3, 4 x cstride
+    const float *p_in_prev, *p_in_cur;   // P_{n-1}, P_n       (ring levels 0-3, or a checkpoint pair)
+    float *p_out_prev, *p_out_cur;       // P_{n+T-1}, P_{n+T} (ring levels 0-3, or a checkpoint pair)
+    const float *in_prev, *in_cur;       // dP_{n-1}, dP_n     (ring levels 4-7)
+    float *out_prev, *out_cur;           // dP_{n+T-1}, dP_{n+T}
+    const float *dam, *ratio, *dbeta, *oscale;   // perturbation workspace (above)
+    float *seis, *dseis;
+    int n0, nsteps;
+    float w[TB_MAXT];                    // wavelet samples w[n0 .. n0+nsteps-1]
+};
+
+// The forward and its tangent in one time loop: k_born_tb with the P levels computed instead of loaded.  The
+// tangent step reads P_n and P_{n-1} only, and the forward step of the same region produces exactly those on
+// exactly the cells the tangent's taps read: at step t of a launch P_{n+t} is exact on the region less 2 t on
+// every side (k_fwd_tb's halo), dP_{n+t+1} is live on the region less 2 (t + 1) and its P taps reach the region
+// less 2 t.  So two P levels are carried in registers beside the two dP levels, P_{n-1}[r] is overwritten with
+// P_{n+1}[r] once the tangent has read it, and no history is read or written.
+//
+// Operation order (contraction off).  d's stencil term and the forward's lap are the same expression of P_n in
+// the same association, so it is evaluated once:
+//   plap = C2 S1(P_n) + C3 S2(P_n)
+//   dP_{n+1} as in k_born_tb (lap, hom, d = 2c1 P_n + plap, f, then + dbeta w[n] at the source cell)
+//   P_{n+1}  = (T1 P_n - T2 P_{n-1}) + A plap, then + beta w[n] at the source cell    (k_fwd_tb's order)
+// with T1 / T2 re-derived from A and K as gen_coef derives them (k_adj_tb, k_born_tb).  The forward's bits are
+// therefore the stored history's bits: dseis is bit-identical to rdq_fwi_born's and seis to rdq_fwi_forward's.
+template <int T, bool GEN>
+__global__ __launch_bounds__(64 * TB_NW) void k_fwd_born_tb(FwdBornTBArgs a)
+{
+    constexpr int H = 2 * T, IW = 64 - 2 * H, IH = TB_RH - 2 * H;
+    __shared__ float xch[2][TB_NW][4][64];
+    __shared__ float pxc[2][TB_NW][4][64];
+    const TBGeo &g = a.g;
+    const int lane = threadIdx.x & 63;
+    const int w = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);   // wave-uniform
+    const TileId ti = decode_tile(blockIdx.x, g.tiles_x, g.ntiles, g.B * g.ns_grp);
+    if (!ti.valid) return;                                            // whole workgroup: uniform
+    const int b = ti.sl / g.ns_grp, s = g.s_off + (ti.sl - b * g.ns_grp), bs = b * g.ns + s;
+    const int ux = ti.tx * IW - H + lane;
+    const int gx = wrapn(ux, g.Wp);
+    const bool xin = lane >= H && lane < 64 - H && ux < g.Wp;
+    const int uz0 = ti.ty * IH - H + w * TB_R;
+    const size_t so = (size_t)bs * g.slice;
+    const float *AL = a.coeffs + (size_t)b * g.slice;
+    const float *KAp = AL + 3 * g.cstride;
+    const int isx = g.isx[s];
+    const float ratio = a.ratio[b], oscale = a.oscale[b];
+    float A[TB_R], K[TB_R], dA[TB_R], D0[TB_R], D1[TB_R], P0[TB_R], P1[TB_R];
+    int rofs[TB_R];
+    unsigned rin = 0, smask = 0;    // wave-uniform row masks: interior and inside the domain; the source row
+    int rrow = -1;                  // wave-uniform: row holding the receivers
+#pragma unroll
+    for (int r = 0; r < TB_R; ++r) {
+        const int uz = uz0 + r, gz = wrapn(uz, g.Hp);
+        rofs[r] = gz * g.ld;
+        const int o = rofs[r] + gx;
+        if constexpr (GEN) {
+            const Coef cf = gen_coef(a.cg, b, gz, gx);
+            A[r] = cf.al; K[r] = cf.kp;
+        } else {
+            A[r] = AL[o]; K[r] = KAp[o];
+        }
+        const int iz = min(max(gz - a.cg.nbc, 0), a.cg.nz - 1), ix = min(max(gx - a.cg.nbc, 0), a.cg.nx - 1);
+        dA[r] = a.dam[((size_t)b * a.cg.nz + iz) * a.cg.nx + ix];
+        D0[r] = a.in_prev[so + o];
+        D1[r] = a.in_cur[so + o];
+        P0[r] = a.p_in_prev[so + o];
+        P1[r] = a.p_in_cur[so + o];
+        const int rr = w * TB_R + r;
+        if (rr >= H && rr < TB_RH - H && uz < g.Hp) rin |= 1u << r;
+        if (gz == g.isz) smask |= 1u << r;      // a region taller than a tiny domain holds the row more than once
+        if (gz == g.igz) rrow = r;
+    }
+    const bool scol = gx == isx;
+    const float bsrc = smask ? a.coeffs[4 * g.cstride + (size_t)b * g.slice + (size_t)g.isz * g.ld + isx] : 0.0f;
+    const float dbsrc = smask ? a.dbeta[bs] : 0.0f;
+    const int rs = (rrow >= 0) ? g.rcv_start[gx] : 0, re = (rrow >= 0) ? g.rcv_start[gx + 1] : 0;
+    const int rcv0 = rs < re ? g.rcv_list[rs] : -1;
+    const bool rmulti = __any(re - rs > 1);               // wave-uniform: a column with several receivers
+#pragma unroll
+    for (int t = 0; t < T; ++t) {
+        if (t >= a.nsteps) break;
+        const int n = a.n0 + t;
+        float *cur = (t & 1) ? D0 : D1;     // dP_n
+        float *prv = (t & 1) ? D1 : D0;     // dP_{n-1} -> overwritten with dP_{n+1}
+        float *P = (t & 1) ? P0 : P1;       // P_n
+        float *Pp = (t & 1) ? P1 : P0;      // P_{n-1}  -> overwritten with P_{n+1}
+        Halo4 hd, hp;
+        const float de[4] = {cur[0], cur[1], cur[TB_R - 2], cur[TB_R - 1]};
+        const float pe[4] = {P[0], P[1], P[TB_R - 2], P[TB_R - 1]};
+        exchange2(xch, pxc, t & 1, w, lane, de, pe, hd, hp);
+#pragma unroll
+        for (int r = 0; r < TB_R; ++r) {
+            TB_VERT(cur, r, hd, zm2, zm1, zp1, zp2)
+            const float c = cur[r];
+            const float xl1 = dpp_shr1(c), xr1 = dpp_shl1(c);
+            const float xl2 = dpp_shr1(xl1), xr2 = dpp_shl1(xr1);
+            float s1 = zm1 + zp1; s1 = s1 + xl1; s1 = s1 + xr1;
+            float s2 = zm2 + zp2; s2 = s2 + xl2; s2 = s2 + xr2;
+            float lap = C2 * s1; const float l2 = C3 * s2; lap = lap + l2;
+            const float kp = K[r];
+            float t1 = C1X2 * A[r]; t1 = t1 + 2.0f; t1 = t1 - kp;     // pde.py:69
+            const float t2 = 1.0f - kp;                               // pde.py:70
+            float hom = t1 * c; const float a2 = t2 * prv[r]; hom = hom - a2;
+            const float a3 = A[r] * lap; hom = hom + a3;
+            TB_VERT(P, r, hp, pm2, pm1, pp1, pp2)
+            const float pc = P[r], pv = Pp[r];
+            const float pl1 = dpp_shr1(pc), pr1 = dpp_shl1(pc);
+            const float pl2 = dpp_shr1(pl1), pr2 = dpp_shl1(pr1);
+            float q1 = pm1 + pp1; q1 = q1 + pl1; q1 = q1 + pr1;
+            float q2 = pm2 + pp2; q2 = q2 + pl2; q2 = q2 + pr2;
+            float plap = C2 * q1; const float pq = C3 * q2; plap = plap + pq;
+            float d = C1X2 * pc; d = d + plap;
+            float f = dA[r] * d;
+            const float dk = kp * ratio, dp = pc - pv;
+            const float fk = dk * dp; f = f - fk;
+            prv[r] = hom + f;
+            float b1 = t1 * pc; const float b2 = t2 * pv; b1 = b1 - b2;   // the forward, k_fwd_tb's order
+            const float b3 = A[r] * plap;
+            Pp[r] = b1 + b3;
+        }
+        if (smask) {                                                   // pde.py:80-81 and its tangent
+#pragma unroll
+            for (int r = 0; r < TB_R; ++r)
+                if ((smask & (1u << r)) && scol) {
+                    const float add = bsrc * a.w[t]; Pp[r] = Pp[r] + add;
+                    const float dadd = dbsrc * a.w[t]; prv[r] = prv[r] + dadd;
+                }
+        }
+        if (rrow >= 0 && (rin & (1u << rrow)) && xin && (n % g.st) == 0) {   // pde.py:82-83
+            float val = 0.0f, dval = 0.0f;
+#pragma unroll
+            for (int r = 0; r < TB_R; ++r) if (r == rrow) { val = Pp[r]; dval = prv[r]; }
+            dval = dval * oscale;
+            const size_t ko = ((size_t)bs * g.nrec + n / g.st) * g.ng;
+            float *SK = a.seis + ko, *DK = a.dseis + ko;
+            if (rcv0 >= 0) { SK[rcv0] = val; DK[rcv0] = dval; }
+            if (rmulti)
+                for (int j = rs + 1; j < re; ++j) { const int k = g.rcv_list[j]; SK[k] = val; DK[k] = dval; }
+        }
+    }
+    if (xin) {
+        const bool odd = (a.nsteps & 1) != 0;   // after nsteps steps the newest levels are in D0 / P0 if odd
+#pragma unroll
+        for (int r = 0; r < TB_R; ++r)
+            if (rin & (1u << r)) {
+                const size_t o = so + rofs[r] + gx;
+                a.out_cur[o] = odd ? D0[r] : D1[r];
+                a.out_prev[o] = odd ? D1[r] : D0[r];
+                a.p_out_cur[o] = odd ? P0[r] : P1[r];
+                a.p_out_prev[o] = odd ? P1[r] : P0[r];
             }
     }
 }
@@ -3123,9 +3282,10 @@ __global__ __launch_bounds__(256) void k_smooth_bwd(int kind, int H, int W, cons
 
 // ======================================================================================= plan
 struct GraphEntry {
-    int kind;                 // 0 fwd-history, 1 fwd-ring, 2 adjoint, 3 fwd-checkpoint, 4 adjoint-checkpoint, 5 born
+    int kind;                 // 0 fwd-history, 1 fwd-ring, 2 adjoint, 3 fwd-checkpoint, 4 adjoint-checkpoint, 5 born,
+                              // 6 fused forward + born
     int B;
-    int K;                    // checkpoint interval (kinds 3, 4; else 0): it shapes the launch sequence
+    int K;                    // checkpoint interval (kinds 3, 4, 6; else 0): it shapes the launch sequence
     const void *ptrs[8];
     hipGraphExec_t exec;
     uint64_t last_use;
@@ -3425,6 +3585,12 @@ KernelRef<BornTBArgs> born_tb_kernel(int T, bool gen)
 {
     return with_depth<TB_MAXT>(T, [&](auto t) -> KernelRef<BornTBArgs> {
         return {gen ? k_born_tb<t(), true> : k_born_tb<t(), false>, 64 * TB_NW};
+    });
+}
+KernelRef<FwdBornTBArgs> fwd_born_tb_kernel(int T, bool gen)
+{
+    return with_depth<TB_MAXT>(T, [&](auto t) -> KernelRef<FwdBornTBArgs> {
+        return {gen ? k_fwd_born_tb<t(), true> : k_fwd_born_tb<t(), false>, 64 * TB_NW};
     });
 }
 
@@ -3851,34 +4017,43 @@ __global__ __launch_bounds__(256) void k_ckpt_levels(const float *src, float *ds
 //   born      the linearised forward: the launches of fwd_ring over the one-segment plan (dP ping-pongs in the
 //             ring), each also reading the stored history (hbase = 0).  Always the narrow kernels (k_born_tb) at
 //             the forward's narrow depth, whatever the plan's wide or persistent settings are.
+//   fwd_born  the forward and its tangent in one loop, no history (k_fwd_born_tb): the launches of fwd_ring over a
+//             CkptPlan, cut at the segment boundaries.  The P pair follows fwd_ring's rule (ring levels 0-3, the
+//             launch ending on an interior boundary writes its pair into the checkpoint store and the next reads
+//             it there); the dP pair (in2 / out2) always ping-pongs in ring levels 4-7.  Narrow kernels at the
+//             forward's narrow depth and chains, as born.
 // The adjoint's levels stay in the ring between launches and the ring parity runs on across segments.
 // Every launch of a chain is ordered on the chain's stream, so a segment's recompute overwrites the
 // segment buffer only after the previous segment's adjoint has read it.
-enum class Pass { fwd_ring, fwd_hist, adj_hist, adj_ckpt, born };
+enum class Pass { fwd_ring, fwd_hist, adj_hist, adj_ckpt, born, fwd_born };
 enum class Store { none, ring, ckpt, hist };
 struct LevelPair {                   // two consecutive levels {slot, slot + 1} of a store (none: nullptr)
     Store store;
     int slot;
 };
 struct Launch {
-    enum Kind { levels, fwd, adj, born } kind;
+    enum Kind { levels, fwd, adj, born, fwd_born } kind;
     int chain, s_off, ns_sh;         // launch chain and its shots [s_off, s_off + ns_sh) of every model
     int first, nsteps;               // fwd: steps first, first + 1, ...; adj: steps first, first - 1, ...
     int seg, hbase;                  // segment, and the slot held by the history buffer's first level
     int tiles_x, ntiles, spw, ns_grp;   // tile grid of the launch's depth, shots per workgroup, shot groups
     unsigned grid;
     LevelPair in, out;               // levels read and written (fwd into a history: out = none)
+    LevelPair in2, out2;             // fwd_born: the dP levels (in / out are its P levels)
 };
+
+// passes that always run the narrow (64-column) kernels at the forward's narrow depth
+bool narrow_pass(Pass pass) { return pass == Pass::born || pass == Pass::fwd_born; }
 
 std::vector<Launch> chunked_schedule(const rdq_fwi_plan *p, int B, Pass pass, const CkptPlan &cp)
 {
-    const bool wide = p->wide && pass != Pass::born;
+    const bool wide = p->wide && !narrow_pass(pass);
     const int Tf = wide ? wide_fwd_depth(p) : p->fwd_T, Ta = chunk_depth(p, true), S = chain_count(p, wide), ns = p->g.ns;
     std::vector<Launch> sched;
     auto add = [&](Launch::Kind kind, int c, int sg, int first, int nsteps, LevelPair in, LevelPair out) {
         Launch l{};
         l.kind = kind; l.chain = c; l.seg = sg; l.first = first; l.nsteps = nsteps; l.in = in; l.out = out;
-        l.hbase = pass == Pass::fwd_ring || pass == Pass::born ? 0 : cp.lo(sg);
+        l.hbase = pass == Pass::fwd_ring || narrow_pass(pass) ? 0 : cp.lo(sg);
         l.s_off = c * ns / S;
         l.ns_sh = (c + 1) * ns / S - l.s_off;
         if (kind != Launch::levels) {
@@ -3896,8 +4071,10 @@ std::vector<Launch> chunked_schedule(const rdq_fwi_plan *p, int B, Pass pass, co
     };
     for (int c = 0; c < S; ++c) {
         int i = 0;                                               // ring parity: runs on across segments
-        if (pass == Pass::fwd_ring || pass == Pass::born) {
-            const Launch::Kind kind = pass == Pass::born ? Launch::born : Launch::fwd;
+        if (pass == Pass::fwd_ring || narrow_pass(pass)) {
+            const Launch::Kind kind = pass == Pass::born       ? Launch::born
+                                      : pass == Pass::fwd_born ? Launch::fwd_born
+                                                               : Launch::fwd;
             for (int sg = cp.nseg - 1; sg >= 0; --sg) {
                 const int lo = cp.lo(sg), hi = cp.hi(sg);
                 for (int n0 = lo; n0 < hi; n0 += Tf, ++i) {
@@ -3905,6 +4082,8 @@ std::vector<Launch> chunked_schedule(const rdq_fwi_plan *p, int B, Pass pass, co
                     add(kind, c, sg, n0, n,
                         n0 == lo && lo > 0 ? LevelPair{Store::ckpt, 2 * sg} : LevelPair{Store::ring, 2 * pin},
                         n0 + n == hi && hi < cp.nt ? LevelPair{Store::ckpt, 2 * (sg - 1)} : LevelPair{Store::ring, 2 * pout});
+                    sched.back().in2 = LevelPair{Store::ring, 4 + 2 * pin};
+                    sched.back().out2 = LevelPair{Store::ring, 4 + 2 * pout};
                 }                                                // (checkpoint sg = pair sg - 1 of the store)
             }
             continue;
@@ -3947,6 +4126,7 @@ struct ChunkBufs {
     double *gk;
     float *gbeta;
     const float *dwork;              // born: the perturbation workspace (`seis` is then the linearised record)
+    float *dseis_out;                // fwd_born: the linearised record (`seis` is the forward's)
 };
 
 int enqueue_chunked(rdq_fwi_plan *p, int B, Pass pass, int K, const ChunkBufs &b, hipStream_t st)
@@ -3955,9 +4135,10 @@ int enqueue_chunked(rdq_fwi_plan *p, int B, Pass pass, int K, const ChunkBufs &b
     FwdTBArgs f{};
     AdjTBArgs a{};
     BornTBArgs d{};
-    f.g = a.g = d.g = tb_geo(p, B);
+    FwdBornTBArgs u{};
+    f.g = a.g = d.g = u.g = tb_geo(p, B);
     const size_t L = a.g.level, slice = a.g.slice;
-    const int S = chain_count(p, p->wide && pass != Pass::born), ns = p->g.ns, nblk_alloc = gk_blocks(p);
+    const int S = chain_count(p, p->wide && !narrow_pass(pass)), ns = p->g.ns, nblk_alloc = gk_blocks(p);
     const bool adjoint = pass == Pass::adj_hist || pass == Pass::adj_ckpt;
     if (adjoint) {   // the gk_part one-writer invariant, on every adjoint launch, before anything is enqueued
         GkWriters writers((size_t)B * ns, nblk_alloc);
@@ -3972,14 +4153,16 @@ int enqueue_chunked(rdq_fwi_plan *p, int B, Pass pass, int K, const ChunkBufs &b
                               {b.gk, (size_t)B * ns * nblk_alloc * sizeof(double)},
                               {b.gbeta, (size_t)B * ns * sizeof(float)}}, st));
     else if (pass == Pass::fwd_hist) RDQ_TRY(zero_regions({{b.hist, 2 * L * sizeof(float)}}, st));
-    else RDQ_TRY(zero_regions({{b.ring, 4 * L * sizeof(float)}}, st));
-    f.coeffs = a.coeffs = d.coeffs = b.coeffs;
-    f.cg = a.cg = d.cg = coef_gen(p, B, b.coeffs);
+    else RDQ_TRY(zero_regions({{b.ring, (pass == Pass::fwd_born ? 8 : 4) * L * sizeof(float)}}, st));   // P, and dP in 4-7
+    f.coeffs = a.coeffs = d.coeffs = u.coeffs = b.coeffs;
+    f.cg = a.cg = d.cg = u.cg = coef_gen(p, B, b.coeffs);
     d.hist = b.hist; d.dseis = b.seis;
     d.dam = b.dwork;
     d.ratio = b.dwork ? b.dwork + (size_t)B * p->g.nz * p->g.nx : nullptr;
     d.dbeta = b.dwork ? d.ratio + B : nullptr;
     d.oscale = b.dwork ? d.dbeta + (size_t)B * p->g.ns : nullptr;
+    u.dam = d.dam; u.ratio = d.ratio; u.dbeta = d.dbeta; u.oscale = d.oscale;
+    u.seis = b.seis; u.dseis = b.dseis_out;
     f.seis = b.seis; f.hist = b.hist;
     a.hist = b.hist; a.dseis = b.dseis; a.gA = b.gA; a.gk_part = b.gk; a.gbeta = b.gbeta;
     a.nblk = nblk_alloc;
@@ -4011,6 +4194,15 @@ int enqueue_chunked(rdq_fwi_plan *p, int B, Pass pass, int K, const ChunkBufs &b
             d.in_prev = level(l.in, 0); d.in_cur = level(l.in, 1);
             d.out_prev = level(l.out, 0); d.out_cur = level(l.out, 1);
             launch_kernel(born_tb_kernel(p->fwd_T, p->fwd_gen), l.grid, cs, d);
+        } else if (l.kind == Launch::fwd_born) {
+            u.g.s_off = l.s_off; u.g.ns_grp = l.ns_grp; u.g.tiles_x = l.tiles_x; u.g.ntiles = l.ntiles;
+            u.n0 = l.first; u.nsteps = l.nsteps;
+            for (int t = 0; t < TB_MAXT; ++t) u.w[t] = t < l.nsteps ? p->wavf[l.first + t] : 0.0f;
+            u.p_in_prev = level(l.in, 0); u.p_in_cur = level(l.in, 1);
+            u.p_out_prev = level(l.out, 0); u.p_out_cur = level(l.out, 1);
+            u.in_prev = level(l.in2, 0); u.in_cur = level(l.in2, 1);
+            u.out_prev = level(l.out2, 0); u.out_cur = level(l.out2, 1);
+            launch_kernel(fwd_born_tb_kernel(p->fwd_T, p->fwd_gen), l.grid, cs, u);
         } else {
             a.g.s_off = l.s_off; a.g.ns_grp = l.ns_grp; a.g.tiles_x = l.tiles_x; a.g.ntiles = l.ntiles;
             a.ns_sh = l.ns_sh; a.spw = l.spw;
@@ -4466,7 +4658,7 @@ int rdq_fwi_sizes(const rdq_fwi_plan *p, int32_t B, rdq_fwi_sizes_t *o)
     o->vstat = (size_t)B * (sizeof(float) + sizeof(int64_t)) + 16;
     o->seis = (size_t)B * ns * p->nrec * p->g.ng * sizeof(float);
     o->history = (size_t)(p->g.nt + 2) * B * ns * slice * sizeof(float);
-    o->ring = 4 * (size_t)B * ns * slice * sizeof(unsigned long long);
+    o->ring = 4 * (size_t)B * ns * slice * sizeof(unsigned long long);   // = 8 float levels (fwd_born: P in 0-3, dP in 4-7)
     if (p->rmulti) o->ring += (size_t)B * ns * p->nrec * p->ncolr * sizeof(float);   // folded residuals
     o->gA = (size_t)B * ns * slice * sizeof(float);
     o->gk_part = (size_t)B * ns * gk_blocks(p) * sizeof(double);
@@ -4598,6 +4790,20 @@ int rdq_fwi_born(const rdq_fwi_plan *pc, int32_t B, const float *coeffs, const f
     b.coeffs = coeffs; b.dwork = dwork; b.hist = const_cast<float *>(hist); b.seis = dseis; b.ring = ring;
     return run_cached(p, 5, B, {coeffs, dwork, hist, dseis, ring}, st,
                       [&](hipStream_t s) { return enqueue_chunked(p, B, Pass::born, p->g.nt, b, s); });
+}
+
+int rdq_fwi_born_fused(const rdq_fwi_plan *pc, int32_t B, int32_t K, const float *coeffs, const float *dwork,
+                       float *seis, float *dseis_out, float *ckpt, float *ring, hipStream_t st)
+{
+    rdq_fwi_plan *p = const_cast<rdq_fwi_plan *>(pc);
+    if (!p || !coeffs || !dwork || !seis || !dseis_out || !ring || B < 1 || (ckpt && K < 1)) return RDQ_E_INVALID;
+    const int Ke = ckpt ? ckpt_plan(p, K).K : p->g.nt;   // no store: one segment
+    std::lock_guard<std::mutex> lk(p->mu);
+    RDQ_TRY(plan_enter(p, st));
+    ChunkBufs b{};
+    b.coeffs = coeffs; b.dwork = dwork; b.seis = seis; b.dseis_out = dseis_out; b.ckpt = ckpt; b.ring = ring;
+    return run_cached(p, 6, B, {coeffs, dwork, seis, dseis_out, ckpt, ring}, st,
+                      [&](hipStream_t s) { return enqueue_chunked(p, B, Pass::fwd_born, Ke, b, s); }, Ke);
 }
 
 int rdq_fwi_ckpt_sizes(const rdq_fwi_plan *p, int32_t B, int32_t K, rdq_fwi_ckpt_sizes_t *o)

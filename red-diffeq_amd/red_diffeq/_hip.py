@@ -93,6 +93,8 @@ SIGNATURES = {
     "rdq_fwi_dcoeffs": (c_int32, [c_void_p, c_int32, c_void_p, ctypes.POINTER(c_int64), c_int32, c_void_p, c_void_p,
                                   c_void_p, c_void_p]),
     "rdq_fwi_born": (c_int32, [c_void_p, c_int32, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p]),
+    "rdq_fwi_born_fused": (c_int32, [c_void_p, c_int32, c_int32, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p,
+                                     c_void_p, c_void_p]),
     "rdq_fwi_grad_finalize": (c_int32, [c_void_p, c_int32, c_void_p, c_void_p, c_void_p, c_void_p,
                                         c_void_p, c_int32, c_void_p, c_void_p, c_void_p]),
     "rdq_l1_partial_bytes": (c_size_t, [c_int32, c_int64]),

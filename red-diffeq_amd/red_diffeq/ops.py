@@ -16,6 +16,9 @@ torch.compile see them as ordinary operators instead of opaque ctypes calls.
         differentiable in v (register_autograd: adjoint + finalize), what FWIForward calls
     red_diffeq::fwi_born(coeffs, vstat, history, dv, plan, B, vel_mode) -> dseis
         the linearised forward J dv over a stored history (FWIForward.born / gauss_newton; no autograd formula)
+    red_diffeq::fwi_born_fused(coeffs, vstat, dv, plan, B, vel_mode, K) -> (seis, dseis, ckpt)
+        the forward and J dv in one time loop with no history (born / gauss_newton with history=False); K = 0: no
+        checkpoints, K >= 1: also fwi_forward_ckpt's store, for fwi_adjoint_ckpt
     red_diffeq::fwi_forward_ckpt(coeffs, plan, B, K) -> (seis, ckpt)               K1, checkpoints every K steps
     red_diffeq::fwi_adjoint_ckpt(coeffs, ckpt, seg, dseis, plan, B, K) -> (gA, gk, gbeta)
         K2 over segments recomputed into the scratch `seg` (the one mutated argument)
@@ -240,6 +243,48 @@ def fwi_born(coeffs: Tensor, vstat: Tensor, history: Tensor, dv: Tensor, plan: i
 @fwi_born.register_fake
 def _(coeffs, vstat, history, dv, plan, B, vel_mode):
     return coeffs.new_empty(_seis_shape(_plan(plan), B))
+
+
+# ---- fused forward + Born pass: seis and J dv in one time loop with no history (rdq_fwi_dcoeffs + rdq_fwi_born_fused)
+def _fused_ckpt_bytes(p, B, K):
+    if K < 0:
+        raise ValueError(f"fwi_born_fused: K must be 0 (no checkpoints) or >= 1, got {K}")
+    return int(p.ckpt_sizes(B, K).ckpt) if K >= 1 else 0
+
+
+@torch.library.custom_op(f"{LIB}::fwi_born_fused", mutates_args=())
+def fwi_born_fused(coeffs: Tensor, vstat: Tensor, dv: Tensor, plan: int, B: int, vel_mode: int,
+                   K: int) -> Tuple[Tensor, Tensor, Tensor]:
+    """(seis, dseis = J dv, ckpt) at the model `coeffs` / `vstat` (fwi_coeffs) belong to.  K = 0: no checkpoints
+    (ckpt is empty); K >= 1: ckpt is fwi_forward_ckpt's store for K steps per segment, for fwi_adjoint_ckpt."""
+    p = _plan(plan)
+    _hip.require_device(coeffs, vstat, dv)
+    sz = p.sizes(B)
+    if tuple(dv.shape) != (B, 1, p.nz, p.nx):
+        raise ValueError("fwi_born_fused: dv does not match the plan")
+    dv = dv.float()
+    nbytes = ctypes.c_size_t()
+    _hip.check(p.lib.rdq_fwi_born_sizes(p.handle, B, ctypes.byref(nbytes)), "rdq_fwi_born_sizes")
+    dwork = _f32(nbytes.value, coeffs.device)
+    ring = _f32(sz.ring, coeffs.device)
+    ckpt = _f32(_fused_ckpt_bytes(p, B, K), coeffs.device)
+    seis = torch.empty(_seis_shape(p, B), dtype=torch.float32, device=coeffs.device)
+    dseis = torch.empty(_seis_shape(p, B), dtype=torch.float32, device=coeffs.device)
+    strides = (ctypes.c_int64 * 4)(*dv.stride())
+    st = _hip.stream_of(coeffs)
+    _hip.check(p.lib.rdq_fwi_dcoeffs(p.handle, B, _hip.ptr(dv), strides, vel_mode, _hip.ptr(coeffs), _hip.ptr(vstat),
+                                     _hip.ptr(dwork), st), "rdq_fwi_dcoeffs")
+    _hip.check(p.lib.rdq_fwi_born_fused(p.handle, B, max(K, 1), _hip.ptr(coeffs), _hip.ptr(dwork), _hip.ptr(seis),
+                                        _hip.ptr(dseis), _hip.ptr(ckpt) if ckpt.numel() else ctypes.c_void_p(0),
+                                        _hip.ptr(ring), st), "rdq_fwi_born_fused")
+    return seis, dseis, ckpt
+
+
+@fwi_born_fused.register_fake
+def _(coeffs, vstat, dv, plan, B, vel_mode, K):
+    p = _plan(plan)
+    return (coeffs.new_empty(_seis_shape(p, B)), coeffs.new_empty(_seis_shape(p, B)),
+            coeffs.new_empty(_fused_ckpt_bytes(p, B, K) // 4))
 
 
 # ---- checkpointed gradient: the history bounded by recomputation (rdq_fwi_forward_ckpt / _adjoint_ckpt)

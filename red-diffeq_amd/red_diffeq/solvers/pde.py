@@ -288,6 +288,16 @@ class FwiPlan:
         settings are; bit-identical for every depth, chain count and graph setting."""
         return torch.ops.red_diffeq.fwi_born(coeffs, vstat, hist, dv, self.op_id, int(B), int(vel_mode))
 
+    def born_fused(self, coeffs, vstat, dv, B, vel_mode, K=None):
+        """(seis, J dv, ckpt) from one time loop that computes the forward and its tangent together and keeps no
+        history (rdq_fwi_born_fused): seis is bit-identical to forward's, J dv to born's.  K = None: no
+        checkpoints (ckpt is empty); K >= 1: ckpt is forward_ckpt(coeffs, B, K)'s store, bit for bit, for
+        adjoint_ckpt.  Narrow chunked kernels at set_tuning's forward depth and chains, as born."""
+        if K is not None and int(K) < 1:
+            raise ValueError(f"born_fused: K must be None or >= 1, got {K}")
+        return torch.ops.red_diffeq.fwi_born_fused(coeffs, vstat, dv, self.op_id, int(B), int(vel_mode),
+                                                   0 if K is None else int(K))
+
     # ---- checkpointed gradient (rdq_fwi_*_ckpt): history bounded by recomputation ----
     def ckpt_sizes(self, B, K):
         """rdq_fwi_ckpt_sizes_t of a checkpointed gradient with K steps per segment: .nseg, .seg_levels,
@@ -463,13 +473,16 @@ class FWIForward(nn.Module):
         return self.s_norm_func(s) if self.normalize else s
 
     # --- linearisation: J dv and the Gauss-Newton product ---------------------------------------
-    def _linearise(self, v, dv, what):
+    def _linearise(self, v, dv, what, need_checkpoint=False):
         """Checks (before any device work), then the model, the direction and vel_mode as K3 takes them, and
         the pull-back of a model gradient through a custom denormalisation (None when it is fused)."""
         if v.dim() != 4 or v.shape[1] != 1:
             raise ValueError(f"{what}: expected v of shape (B,1,H,W), got {tuple(v.shape)}")
         if tuple(dv.shape) != tuple(v.shape):
             raise ValueError(f"{what}: dv has shape {tuple(dv.shape)}, v {tuple(v.shape)}")
+        if need_checkpoint and self.checkpoint is None and self.history_budget_gb is None:
+            raise ValueError(f"{what}(history=False) runs its adjoint over checkpoints: construct FWIForward with "
+                             f"checkpoint=K or history_budget_gb (neither is set)")
         _hip.require_device(v, dv)
         v, dv = v.detach().float(), dv.detach().float()
         if self._fused_denorm():
@@ -488,42 +501,72 @@ class FWIForward(nn.Module):
         need = int(plan.sizes(B).history)
         if self.history_budget_gb is not None and need > int(float(self.history_budget_gb) * 2 ** 30):
             raise ValueError(f"born / gauss_newton keep a store-all history of {need} bytes, more than "
-                             f"history_budget_gb = {self.history_budget_gb}; a checkpointed Born pass does not exist")
+                             f"history_budget_gb = {self.history_budget_gb}; pass history=False for the fused "
+                             f"pass, which keeps no history")
         coeffs, vstat = plan.coeffs(v, vel_mode)
         seis, hist = plan.forward(coeffs, B, True)
         return plan, coeffs, vstat, hist, seis, plan.born(coeffs, vstat, hist, dv, B, vel_mode)
 
+    def _born_fused(self, v, dv, vel_mode, checkpoints):
+        """K3, the Born prologue and the fused forward + tangent time loop: no history, no budget check.
+        `checkpoints`: also the checkpoint store of this instance's interval, for the checkpointed adjoint."""
+        plan = self._plan(v.shape[2], v.shape[3], v.device)
+        self._last = plan
+        B = v.shape[0]
+        K = None
+        if checkpoints:
+            K = self.checkpoint_interval(plan, B)
+            if K is None:                        # the whole history fits the budget: one segment, no store
+                K = plan.nt
+        coeffs, vstat = plan.coeffs(v, vel_mode)
+        seis, ds, ckpt = plan.born_fused(coeffs, vstat, dv, B, vel_mode, K)
+        return plan, coeffs, vstat, ckpt, K, seis, ds
+
     def _custom_s_norm(self):
         return self.normalize and self.s_norm_func is not s_normalize_none
 
-    def born(self, v, dv, return_seis=False):
+    def born(self, v, dv, return_seis=False, history=True):
         """Linearised (Born) modelling: J dv, J = d forward(v) / d v, with the shape of forward(v); with
-        return_seis, (forward(v), J dv).  Runs under no_grad on a store-all history (ValueError with the byte
-        count when history_budget_gb is set and it does not fit); the result does not require grad.  A custom
-        v_denorm_func, and an s_norm_func other than s_normalize_none, are chained with torch.func.jvp.  With
-        shots=, this rank's shots only, as forward."""
+        return_seis, (forward(v), J dv).  Runs under no_grad; the result does not require grad.  history=True
+        (the default): the forward keeps its store-all history and the Born pass streams it back (ValueError with
+        the byte count when history_budget_gb is set and it does not fit).  history=False: one fused time loop
+        computes the forward and its tangent together and keeps no history at all (no budget applies); both
+        outputs are bit-identical to history=True's.  A custom v_denorm_func, and an s_norm_func other than
+        s_normalize_none, are chained with torch.func.jvp.  With shots=, this rank's shots only, as forward."""
         v, dv, vel_mode, _ = self._linearise(v, dv, "born")
         with torch.no_grad():
-            seis, ds = self._born(v, dv, vel_mode)[4:]
+            if history:
+                seis, ds = self._born(v, dv, vel_mode)[4:]
+            else:
+                seis, ds = self._born_fused(v, dv, vel_mode, False)[5:]
         if self._custom_s_norm():
             seis, ds = torch.func.jvp(self.s_norm_func, (seis,), (ds,))
         seis, ds = seis.detach(), ds.detach()
         return (seis, ds) if return_seis else ds
 
-    def gauss_newton(self, v, dv, weight=None):
-        """The Gauss-Newton product J^T (weight * J dv), with the shape of v: one forward with history, one Born
-        pass, then the adjoint and the finalize on the same history (no second forward).  Bit-equal to
-        s = forward(v); s.backward(weight * born(v, dv)); v.grad."""
-        v, dv, vel_mode, pull = self._linearise(v, dv, "gauss_newton")
+    def gauss_newton(self, v, dv, weight=None, history=True):
+        """The Gauss-Newton product J^T (weight * J dv), with the shape of v.  history=True (the default): one
+        forward with history, one Born pass, then the adjoint and the finalize on the same history (no second
+        forward).  Bit-equal to s = forward(v); s.backward(weight * born(v, dv)); v.grad.  history=False: the
+        fused forward + Born pass, which also writes the checkpoint store of checkpoint_interval(), then the
+        checkpointed adjoint and the finalize: the memory of a checkpointed gradient, bit-equal to the same
+        three lines on this instance.  It needs checkpoint= or history_budget_gb (ValueError otherwise)."""
+        v, dv, vel_mode, pull = self._linearise(v, dv, "gauss_newton", need_checkpoint=not history)
         with torch.no_grad():
-            plan, coeffs, vstat, hist, seis, ds = self._born(v, dv, vel_mode)
+            if history:
+                plan, coeffs, vstat, hist, seis, ds = self._born(v, dv, vel_mode)
+            else:
+                plan, coeffs, vstat, hist, K, seis, ds = self._born_fused(v, dv, vel_mode, True)
         if self._custom_s_norm():
             ds = torch.func.jvp(self.s_norm_func, (seis,), (ds,))[1]
         r = ds if weight is None else weight * ds
         if self._custom_s_norm():
             r = torch.func.vjp(self.s_norm_func, seis)[1](r)[0]
         with torch.no_grad():
-            gA, gk, gb = plan.adjoint(coeffs, hist, r.detach().contiguous(), v.shape[0])
+            if history:
+                gA, gk, gb = plan.adjoint(coeffs, hist, r.detach().contiguous(), v.shape[0])
+            else:
+                gA, gk, gb = plan.adjoint_ckpt(coeffs, hist, r.detach().contiguous(), v.shape[0], K)
             del hist
             g = plan.finalize(coeffs, vstat, gA, gk, gb, v.shape[0], vel_mode)
         return (g if pull is None else pull(g)).detach()

@@ -10,7 +10,14 @@ per leg (ms as median and min - max), printed and appended to --out:
   adj_narrow         the narrow chunked adjoint over the same history: the Born pass's yardstick, it reads the same
                      history stream and does the same two stencils per step
   gauss_newton       FWIForward.gauss_newton on the plan's defaults: forward with history + Born + adjoint + finalize
---no-born runs only the legs that need no Born interface, so the script can be pointed at an earlier checkout.
+  born               FWIForward.born on the plan's defaults: K3 + forward with history + Born prologue and pass
+  born_fused         FWIForward.born(history=False): K3 + prologue + the fused forward + tangent pass, no history
+  gauss_newton_fused FWIForward(checkpoint=40).gauss_newton(history=False): the fused pass writing the checkpoint
+                     store, the checkpointed adjoint (recompute + adjoint per segment), finalize
+The last four legs also report peak_bytes: the rise of torch.cuda.max_memory_allocated over one call (measured in
+a pass of its own after the timed repeats).
+--no-born runs only the legs that need no Born interface and --no-fused leaves out the history=False legs, so the
+script can be pointed at an earlier checkout.
 
 python tools/bench_born.py [--reps 7] [--no-born] [--out profiles/r14/born.jsonl]"""
 import argparse
@@ -31,6 +38,7 @@ ap = argparse.ArgumentParser()
 ap.add_argument("--reps", type=int, default=7)
 ap.add_argument("--warmup", type=int, default=2)
 ap.add_argument("--no-born", action="store_true")
+ap.add_argument("--no-fused", action="store_true")
 ap.add_argument("--label", default="")
 ap.add_argument("--out", default=os.path.join(ROOT, "profiles", "r14", "born.jsonl"))
 a = ap.parse_args()
@@ -66,6 +74,12 @@ if not a.no_born:
     legs["born_pass"] = lambda: plan.born(coeffs, vstat, hist, dv, 1, 0)
     legs["born_pass_fields"] = lambda: fplan.born(coeffs, vstat, hist, dv, 1, 0)
     legs["gauss_newton"] = lambda: default.gauss_newton(v, dv)
+    legs["born"] = lambda: default.born(v, dv)
+    if not a.no_fused:
+        ckpt40 = FWIForward(dict(ctx), dev, v_denorm_func=v_denormalize, s_norm_func=s_normalize_none, checkpoint=40)
+        legs["born_fused"] = lambda: default.born(v, dv, history=False)
+        legs["gauss_newton_fused"] = lambda: ckpt40.gauss_newton(v, dv, history=False)
+NARROW = ("fwd_hist_narrow", "adj_narrow", "born_pass", "born_pass_fields")
 times = {name: [] for name in legs}
 with torch.no_grad():
     for i in range(a.warmup + a.reps):          # the legs alternate: drift hits all of them alike
@@ -78,13 +92,30 @@ with torch.no_grad():
             torch.cuda.synchronize()
             if i >= a.warmup:
                 times[name].append(e0.elapsed_time(e1))
+peak = {}
+for name in ("born", "born_fused", "gauss_newton", "gauss_newton_fused"):
+    if name in legs:
+        torch.cuda.synchronize()
+        torch.cuda.reset_peak_memory_stats()
+        base = torch.cuda.memory_allocated()
+        legs[name]()
+        torch.cuda.synchronize()
+        peak[name] = torch.cuda.max_memory_allocated() - base
 narrow.check()
 default.check()
 os.makedirs(os.path.dirname(os.path.abspath(a.out)), exist_ok=True)
 for name, t in times.items():
     rec = {"leg": name, "grid": [nz, nx], "nbc": ctx["nbc"], "ns": ctx["ns"], "nt": ctx["nt"], "B": 1,
            "ms_median": round(statistics.median(t), 3), "ms_min": round(min(t), 3), "ms_max": round(max(t), 3),
-           "reps": len(t), "launch": (default if name == "gauss_newton" else narrow)._plan(nz, nx, dev).launch_info(1)}
+           "reps": len(t), "launch": (narrow if name in NARROW else default)._plan(nz, nx, dev).launch_info(1)}
+    if name == "born_fused":                  # no persistent or wide kernel runs in this leg
+        depth = rec["launch"]["fwd_T"]
+        rec["launch"] = f"narrow chunked fused pass, {-(-ctx['nt'] // depth)} launches of {depth} steps"
+    if name == "gauss_newton_fused":
+        rec["launch"] = dict(ckpt40._plan(nz, nx, dev).ckpt_info(1, 40), fused="narrow chunked fused pass, K = 40")
+    if name in peak:
+        rec["peak_bytes"] = peak[name]
+        rec["history_bytes"] = int(default._plan(nz, nx, dev).sizes(1).history)
     if a.label:
         rec["label"] = a.label
     print(json.dumps(rec), flush=True)
