@@ -177,7 +177,8 @@ int rdq_fwi_set_wave_roles(rdq_fwi_plan *plan, int32_t fwd_mode, int32_t adj_mod
  *              value, the wavelet loads and the record), and the waves with neither row run the guard-free
  *              loop (no source / receiver / history / end-of-record test, no wavelet loads); configs[1]:
  *              1.034 -> 0.958 ms;
- *   adjoint:   0 only: every form of the role tried there spilled more registers than the kernel does now.
+ *   adjoint:   0 only here (RDQ_E_INVALID otherwise): the adjoint's role has a setter of its own,
+ *              rdq_fwi_set_adjoint_role.
  * Built at 4 steps per epoch and 6 rows per wave of the 96-row regions; not run where the source row has a
  * live halo copy in a neighbouring region, by a call that keeps no history, or at other depths, rows per wave
  * or region classes: those run the generic loop (rdq_fwi_source_role_info reports the mode that runs).  Per
@@ -187,6 +188,28 @@ int rdq_fwi_set_source_role(rdq_fwi_plan *plan, int32_t fwd_mode, int32_t adj_mo
 /* out = {the source-role mode the forward of a call with batch B runs, the same for the adjoint (0)}; 0 for
  * chunked launches. */
 int rdq_fwi_source_role_info(rdq_fwi_plan *plan, int32_t B, int32_t out[2]);
+/* Source/receiver role of the persistent (recurrence) adjoint; mode 0 / 1, default 1 (RDQ_E_INVALID for any
+ * other mode, nothing changed):
+ *   1: the wave whose rows own the source row, where that row is the receiver row too, runs every epoch but the
+ *      last in a loop of its own: the guard-free step plus the row's own work (the receiver residual's add, the
+ *      source term's undo and the gbeta term of the gradient, the next epoch's sample and residual loads) with
+ *      the row's pair a compile-time constant.  The pair is the same for every tile, shot and model, so the
+ *      host picks the kernel built for it;
+ *   0: that wave runs the generic loop.
+ * Runs where the forward's source role would (4 steps per epoch, 6 rows per wave of the 96-row regions,
+ * isz == igz, sample_temporal 1, no live halo copy of the row) and only with the adjoint's wave roles on
+ * (rdq_fwi_set_wave_roles) in the recurrence adjoint; the phase-profiled build has no role.  Per cell the
+ * operations and their order are the same: results are bit-identical in both modes.  Changing the mode drops
+ * the plan's cached graphs. */
+int rdq_fwi_set_adjoint_role(rdq_fwi_plan *plan, int32_t mode);
+/* out = {the adjoint-role mode the adjoint of a call with batch B runs (0 for chunked launches), the mirrored
+ * row pair 0..2 of the source/receiver row in the wave that owns it, or -1 where the role does not run}.  A
+ * launch that ran the role leaves in status word 24 (rdq_fwi_debug_words) the number of waves that entered the
+ * role's loop: one per workgroup whose interior rows own the source row; the word is zeroed by every
+ * persistent adjoint call. */
+int rdq_fwi_adjoint_role_info(rdq_fwi_plan *plan, int32_t B, int32_t out[2]);
+/* The mirrored row pair (0..2) the role uses for padded row `padded_row` (>= 0; host only, no plan). */
+int rdq_fwi_role_row_pair(int32_t padded_row);
 /* 1 (default) = run each time loop as ONE persistent launch (regions resident in registers for
  * all nt steps, epoch-wise neighbour hand-offs) whenever the whole grid fits resident on the
  * device: small surveys (at most 200 workgroups, e.g. 3 OpenFWI shots) in 64 x 64 regions of 16

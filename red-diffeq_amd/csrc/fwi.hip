@@ -1646,6 +1646,7 @@ __global__ __launch_bounds__(64 * NW) void k_adj_tw(AdjTBArgs a)
 constexpr int CP_SC1 = 16;                            // buffer cache policy: sc1 (write-through / L1 bypass)
 constexpr int PT_ADJ_SG = 8;                          // adjoint hand-off sweep: rows per load group
 constexpr int PT_ROLES_T = 4;                         // wave roles (rdq_fwi_set_wave_roles) are built at this depth
+constexpr int PT_ROLE_WORD = 24;                      // status word: waves that entered the adjoint's source/receiver loop
 constexpr int PT_SROLE_RW = 6;                        // the source role (rdq_fwi_set_source_role): that depth, these rows per wave
 constexpr size_t PROF_RAW = 16;                       // per-wave records after the 11 summary words (PT_PROF_FLUSH)
 constexpr size_t PROF_REC = 8;                        // words per wave record
@@ -2656,8 +2657,13 @@ __global__ __launch_bounds__(64 * NW) void k_adj_pt(AdjPtArgs a)
     {                                                                                               \
         const int so_ = (SOFF);                                                                     \
         _Pragma("unroll") for (int i = 0; i < RP; ++i) {                                             \
-            PD[i].x = bload_nt(HR, pr[i], so_);                                                     \
-            PD[i].y = bload_nt(HR, pr[R - 1 - i], so_);   /* mirrored pairs {i, R-1-i} */          \
+            if constexpr (PR_S) {                    /* one lane offset, the row in the scalar offset */ \
+                PD[i].x = bload_nt(HR, pl, so_ + prs[i]);                                           \
+                PD[i].y = bload_nt(HR, pl, so_ + prs[R - 1 - i]);                                   \
+            } else {                                                                                \
+                PD[i].x = bload_nt(HR, pr[i], so_);                                                 \
+                PD[i].y = bload_nt(HR, pr[R - 1 - i], so_);   /* mirrored pairs {i, R-1-i} */      \
+            }                                                                                       \
         }                                                                                           \
     }
 
@@ -2674,7 +2680,14 @@ __global__ __launch_bounds__(64 * NW) void k_adj_pt(AdjPtArgs a)
         }                                                                                           \
         int sg_ = RL_PLAIN ? -1 : srow;              /* one scalar branch for both source terms */  \
         if constexpr (!RL_PLAIN) LAUNDER(sg_);       /* (plain role: no source row) */              \
-        if (sg_ >= 0) {                                                                             \
+        if constexpr (RL_SR >= 0) {                  /* source/receiver role: the row's pair is RL_SR */ \
+            const float sa_ = scol ? bsrc * (WK) : 0.0f;                                            \
+            const f32x2 sv_ = shalf ? f32x2{0.0f, sa_} : f32x2{sa_, 0.0f};                          \
+            u[SRP] = u[SRP] - sv_;                                                                  \
+            const float ls_ = shalf ? LN[SRP].y : LN[SRP].x;                                        \
+            const float gb = scol ? ls_ * (WK) : -0.0f;                                             \
+            gbacc = gbacc + gb;                                                                     \
+        } else if (sg_ >= 0) {                                                                      \
             int sp_ = spair;                                                                        \
             LAUNDER(sp_);                                                                           \
             const float sa_ = scol ? bsrc * (WK) : 0.0f;  /* the forward's source add, undone */    \
@@ -2719,7 +2732,10 @@ __global__ __launch_bounds__(64 * NW) void k_adj_pt(AdjPtArgs a)
         }                                                                                           \
         int rr_ = RL_PLAIN ? 0 : (LO) == 0 ? rlo : rhi;   /* the receiver's pair is in this half */ \
         if constexpr (!RL_PLAIN) LAUNDER(rr_);       /* (plain role: no receiver row) */            \
-        if ((HI) > (LO) && rr_ && rec_index(k - 1, g.st) >= 0) {                                    \
+        if constexpr (RL_SR >= 0) {                  /* source/receiver role: every step is recorded */ \
+            if constexpr ((HI) > (LO) && SRP >= (LO) && SRP < (HI))                                 \
+                PRV[SRP] = PRV[SRP] + (shalf ? f32x2{-0.0f, dcur} : f32x2{dcur, -0.0f});            \
+        } else if ((HI) > (LO) && rr_ && rec_index(k - 1, g.st) >= 0) {                             \
             int rp_ = rpair;                                                                        \
             LAUNDER(rp_);                                                                           \
             const f32x2 dv_ = rhalf ? f32x2{-0.0f, dcur} : f32x2{dcur, -0.0f};   /* -0: no-op */     \
@@ -2751,13 +2767,16 @@ __global__ __launch_bounds__(64 * NW) void k_adj_pt(AdjPtArgs a)
 // 1.4911 -> 1.4722, kernel_ab_adj_shadow_fwd_xmfirst.jsonl).  In the forward the zeroing in the round
 // trip was slower (1.011 -> 1.035 ms: more stale first passes) and the lean form after the sweep no
 // faster, so the forward has the one order.
-template <int T, int NW, int RW, bool PROF, int OV = 0>
+template <int T, int NW, int RW, bool PROF, int OV = 0, int SR = -1>
 __global__ __launch_bounds__(64 * NW) void k_adj_pr(AdjPtArgs a)
 {
     unsigned long long *const prof = PROF ? a.prof : nullptr;   // phase counters: profiled build only
     constexpr bool PT_PRIO = true;                        // wave priorities (PT_PRIO_*)
     constexpr bool PT_MIR = true;                         // mirrored pairs for the exchange's boundary rows
     constexpr bool RL_PLAIN = false;                      // the generic wave role (shadowed in the plain epochs)
+    constexpr int RL_SR = -1, SRP = 0;                    // source/receiver role: the row's pair (SRP = max(RL_SR, 0))
+    constexpr bool PR_S = SR >= 0;                        // history row offsets as scalars (ADJR_LOAD)
+    static_assert(SR < RW / 2 && (SR < 0 || (T == PT_ROLES_T && RW == PT_SROLE_RW)), "k_adj_pr: the role's row pair");
     __shared__ XmBox<NW> xm;                              // the waves' inboxes (xm_*)
     __shared__ double red[64 * NW];
     // the LDS the residency decision (resident_capacity) depends on: the mailboxes and the reduction
@@ -2804,10 +2823,21 @@ __global__ __launch_bounds__(64 * NW) void k_adj_pr(AdjPtArgs a)
     const size_t L = g.level;
     const int L4 = (int)(L * 4);                          // bytes per history slot (< 2 GB: resident surveys)
     f32x2 Q0[RP], Q1[RP], Q2[RP], Q3[RP];
+    // History offsets of ADJR_LOAD, in two forms, of which a build reads one (`if constexpr (PR_S)` there) and
+    // the compiler drops the other.  Builds without a source/receiver role (SR = -1) read pr[r]: the offset of
+    // (own row r, lane), a VGPR each.
     int pr[R];                                            // history offset of (own row r, lane)
 #pragma unroll
     for (int r = 0; r < R; ++r)   // every lane (own cells only, halo lanes at OOB: 1.66 -> 1.73 ms)
         pr[r] = grad ? (PT_ROFS(r) + gx) * 4 : OOB;
+    // Builds with a role (PR_S) read the same offsets as one lane offset pl and a wave-uniform row offset
+    // prs[r] that goes into the load's scalar offset: six VGPRs less, six SGPRs more.  (Both forms are written
+    // out unguarded on purpose: with each under its own `if constexpr` the SR >= 0 builds come out as a
+    // different text, 133 SGPR spills for 131, and the text here is the one that was timed.)
+    const int pl = grad ? gx * 4 : OOB;
+    int prs[R];
+#pragma unroll
+    for (int r = 0; r < R; ++r) prs[r] = __builtin_amdgcn_readfirstlane(PT_ROFS(r) * 4);
 #pragma unroll
     for (int i = 0; i < RP; ++i) { Q0[i] = 0.0f; Q1[i] = 0.0f; Q2[i] = 0.0f; Q3[i] = 0.0f; }
     // history descriptor of the epoch whose first step is KN: its prefetches read slots
@@ -2886,7 +2916,7 @@ __global__ __launch_bounds__(64 * NW) void k_adj_pr(AdjPtArgs a)
             if constexpr (OV == 0) PT_SWEEP(GR, tag, L0, L1, PT_ADJ_SG)                             \
             else PT_SWEEP_SHADOW(GR, tag, L0, L1, PT_ADJ_SG, (PT_ADJ_SG < R ? PT_ADJ_SG : R))       \
             xm_put<NW>(xm, (e + 1) * T & 1, w, lane, (unsigned)((e + 1) * T) + 1u, A[0] * L1[0], A[1] * L1[1]); \
-            if constexpr (!RL_PLAIN) ADJ_ISSUE                                                      \
+            if constexpr (!RL_PLAIN || RL_SR >= 0) ADJ_ISSUE                                        \
             PT_PROF_TAIL                                                                            \
         }                                                                                           \
         if constexpr ((T & 3) != 0) {                                                               \
@@ -2906,8 +2936,18 @@ __global__ __launch_bounds__(64 * NW) void k_adj_pr(AdjPtArgs a)
     // text in both, and per cell the arithmetic is the same: results are bit for bit those of mode 0.
     // configs[1]: 1.4464 -> 1.4193 ms (profiles/r11/kernel_ab_adj_roles.jsonl).  (One loop choosing a body
     // per epoch spilled 107 VGPRs; the same split of the forward's steps alone was no faster: the forward has
-    // it with its source role, k_fwd_pt.  A source role here spilled 11 to 413 values in the three forms tried,
-    // profiles/r13/resource_usage.txt, and is not built.)
+    // it with its source role, k_fwd_pt.)
+    // Source/receiver role (rdq_fwi_set_adjoint_role), SR >= 0: the wave whose rows own the source row, that row
+    // being the receiver row too, in mirrored pair SR (the host's choice, adjoint_role_pair: the pair is the same
+    // for every tile, shot and model of a launch, so it is a template parameter and each build carries one such
+    // body).  That wave branches once into a loop of its own over every epoch but the last: the plain epoch plus
+    // the row's work with the pair a compile-time index and the half a scalar (the receiver add in
+    // ADJR_PAIRS_NB, the source undo and the gbeta term in ADJR_GRAD, ADJ_ISSUE after the sweep).  The host
+    // runs it only where every step is recorded and the row has no live halo copy (source_role_fits).  With the
+    // pair a run-time value or one body per pair in one kernel the role spilled 11 to 413 VGPR values
+    // (profiles/r13/resource_usage.txt); as built it needs the history row offsets as scalars (PR_S) to spill
+    // none (profiles/r18/resource_usage.txt).  The waves that enter count themselves into status word
+    // PT_ROLE_WORD, once per launch.  Same text per cell as the generic step: bit for bit the results of SR = -1.
     int e = 0;
     if constexpr (T == PT_ROLES_T) {
         if (plain) {
@@ -2915,6 +2955,17 @@ __global__ __launch_bounds__(64 * NW) void k_adj_pr(AdjPtArgs a)
             for (; e + 1 < nep; ++e) ADJR_EPOCH
             const int kn = a.nt - e * T;                  // the generic epoch's samples and residuals
             ADJ_ISSUE
+        }
+        // (a test of its own after the plain branch, which a plain wave fails: as the plain branch's `else`
+        // the same text spills 24 to 54 VGPR values around the loops, profiles/r18/resource_usage.txt)
+        int srw = SR >= 0 && a.roles && srow >= 0 && rrow == srow && spair == SR;
+        srw = __builtin_amdgcn_readfirstlane(srw);
+        if (srw) {
+            constexpr bool RL_PLAIN = true;
+            constexpr int RL_SR = SR, SRP = SR;
+            if (lane == 0)                                // once per wave and launch: the role ran
+                __hip_atomic_fetch_add(a.status + PT_ROLE_WORD, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+            for (; e + 1 < nep; ++e) ADJR_EPOCH
         }
     }
     for (; e < nep; ++e) ADJR_EPOCH
@@ -3328,6 +3379,7 @@ struct rdq_fwi_plan {
     int adj_ov = RDQ_OVERLAP_ADJ;   // the persistent (recurrence) adjoint's hand-off overlap mode
     int adj_roles = 1;              // wave roles of the persistent (recurrence) adjoint (rdq_fwi_set_wave_roles)
     int fwd_srole = RDQ_SROLE_FWD;  // source role of the persistent forward (rdq_fwi_set_source_role)
+    int adj_srole = 1;              // source/receiver role of the persistent adjoint (rdq_fwi_set_adjoint_role)
     int adj_Tw = 0;             // the wide chunked adjoint's depth (<= TW_ADJ_MAXT); 0 = auto, see wide_adj_depth
     int fwd_Tw = 0;             // the wide chunked forward's depth (<= TW_FWD_MAXT); 0 = auto, see wide_fwd_depth
     int adj_spw = 0;            // the wide chunked adjoint's shots per workgroup, 0 = auto (wide_spw)
@@ -3712,9 +3764,42 @@ bool source_role_fits(const rdq_fwi_plan *p, int NW, int T, int rw)
 // The source-role mode a persistent forward launch runs (0 = none); it covers the plain loop too.  (A no-grad
 // call keeps no history and runs the generic loop whatever the mode.)
 int fwd_source_role(const rdq_fwi_plan *p, int NW) { return p->fwd_srole && source_role_fits(p, NW, p->fwd_T, p->fwd_rw); }
+// Mirrored row pair (k_adj_pr's SR) of padded row `row` in the region that owns it: 96-row regions at
+// PT_ROLES_T steps per epoch and PT_SROLE_RW rows per wave.  The owning tile row, the wave and the row in the
+// wave depend on the row alone (PT_REGION_GEOM: own rows are region rows H .. RH - H - 1 of tile row row / IH),
+// so the pair is the same for every tile, shot and model of a launch.
+int role_row_pair(int row)
+{
+    constexpr int H = 2 * PT_ROLES_T, IH = 96 - 2 * H, R = PT_SROLE_RW;
+    const int r = (row % IH + H) % R;                    // row in wave of region row (row - ty IH) + H
+    return r < R / 2 ? r : R - 1 - r;
+}
+// Whether the persistent adjoint of region class NW runs its source/receiver role (rdq_fwi_set_adjoint_role),
+// and with which row pair (-1 = no role): the recurrence adjoint with wave roles on, in a launch the source
+// role fits (source_role_fits); the phase-profiled build has no role.  The one place that decides it: the
+// kernel table, the capacity query and rdq_fwi_adjoint_role_info all ask here.
+int adjoint_role_pair(const rdq_fwi_plan *p, int NW, bool prof)
+{
+    if (!p->adj_srole || prof || !p->adj_fma || adj_wave_roles(p) != 1) return -1;
+    if (!source_role_fits(p, NW, p->adj_T, p->adj_rw)) return -1;
+    return role_row_pair(p->g.isz);
+}
+template <int OV>
+KernelRef<AdjPtArgs> adj_pr_role(int sr)
+{
+    constexpr int T = PT_ROLES_T, RW = PT_SROLE_RW;
+    if (sr == 0) return {k_adj_pr<T, 16, RW, false, OV, 0>, 64 * 16};
+    if (sr == 1) return {k_adj_pr<T, 16, RW, false, OV, 1>, 64 * 16};
+    return {k_adj_pr<T, 16, RW, false, OV, 2>, 64 * 16};
+}
 KernelRef<AdjPtArgs> adj_pt_kernel(const rdq_fwi_plan *p, int NW, int T, bool fma, bool prof)
 {
     static_assert(PT_OV_T == 4, "the profiled and the overlap builds share their depth");
+    static_assert(PT_ROLES_T == 4 && PT_SROLE_RW / 2 == 3, "adj_pr_role: the role's depth and its three row pairs");
+    if (T == p->adj_T && fma == p->adj_fma) {
+        const int sr = adjoint_role_pair(p, NW, prof);
+        if (sr >= 0) return adj_overlap(p) ? adj_pr_role<1>(sr) : adj_pr_role<0>(sr);
+    }
     if (T == 4 && fma && adj_overlap(p))
         return prof ? adj_pt_T<4, true, 1>(NW, p->adj_rw, true) : adj_pt_T<4, false, 1>(NW, p->adj_rw, true);
     if (prof && T == 4) return adj_pt_T<4, true>(NW, p->adj_rw, fma);
@@ -3738,12 +3823,14 @@ int resident_capacity(rdq_fwi_plan *p, KernelRef<Args> k)
 }
 
 // Resident capacity of the persistent kernel a call would launch.  The adjoint's launch must fit both
-// adjoint variants of the class, whichever one adj_fma selects.
+// adjoint variants of the class, whichever one adj_fma selects; each is asked for as launch_adjoint_pt asks
+// (the phase-profiled build while the profile is on: it has no source/receiver role).
 int capacity_nw(rdq_fwi_plan *p, int NW, bool adj, int T)
 {
     if (!adj) return resident_capacity(p, fwd_pt_kernel(p, NW, T, false));
-    return std::min(resident_capacity(p, adj_pt_kernel(p, NW, T, false, false)),
-                    resident_capacity(p, adj_pt_kernel(p, NW, T, true, false)));
+    const bool prof = p->d_prof != nullptr;
+    return std::min(resident_capacity(p, adj_pt_kernel(p, NW, T, false, prof)),
+                    resident_capacity(p, adj_pt_kernel(p, NW, T, true, prof)));
 }
 
 // rows of a persistent region of class NW (fwd_pt_T)
@@ -3941,7 +4028,9 @@ int launch_adjoint_pt(rdq_fwi_plan *p, int B, int NW, int per, const float *coef
     const int nblk_alloc = gk_blocks(p);
     if (int e = zero_regions({{ring, 4 * L * sizeof(unsigned long long)}, {gA, L * sizeof(float)},
                               {gk, (size_t)B * p->g.ns * nblk_alloc * sizeof(double)},
-                              {gbeta, (size_t)B * p->g.ns * sizeof(float)}, {p->d_status + 16, 8 * sizeof(unsigned)}},
+                              {gbeta, (size_t)B * p->g.ns * sizeof(float)},
+                              // the arrival counters and, behind them, the call's role-wave count (PT_ROLE_WORD)
+                              {p->d_status + 16, (PT_ROLE_WORD + 1 - 16) * sizeof(unsigned)}},
                              st))
         return e;
     const int ih = region_rows(NW) - 4 * T;
@@ -4526,7 +4615,7 @@ int rdq_fwi_set_wave_roles(rdq_fwi_plan *p, int32_t fwd_mode, int32_t adj_mode)
 
 int rdq_fwi_set_source_role(rdq_fwi_plan *p, int32_t fwd_mode, int32_t adj_mode)
 {
-    if (!p || fwd_mode < 0 || fwd_mode > 1 || adj_mode != 0) return RDQ_E_INVALID;   // the adjoint has no such role
+    if (!p || fwd_mode < 0 || fwd_mode > 1 || adj_mode != 0) return RDQ_E_INVALID;   // the adjoint's role has its own setter (rdq_fwi_set_adjoint_role)
     std::lock_guard<std::mutex> lk(p->mu);
     set_knob(p, p->fwd_srole, fwd_mode);   // (drops the cached graphs when the value changes)
     return 0;
@@ -4538,9 +4627,29 @@ int rdq_fwi_source_role_info(rdq_fwi_plan *p, int32_t B, int32_t out[2])
     std::lock_guard<std::mutex> lk(p->mu);
     const int nwf = persistent_nw(p, B, false);
     out[0] = nwf ? fwd_source_role(p, nwf) : 0;
-    out[1] = 0;   // the adjoint has the generic and the plain loop only
+    out[1] = 0;   // the adjoint's role has a setting of its own (rdq_fwi_set_adjoint_role)
     return 0;
 }
+
+int rdq_fwi_set_adjoint_role(rdq_fwi_plan *p, int32_t mode)
+{
+    if (!p || mode < 0 || mode > 1) return RDQ_E_INVALID;
+    std::lock_guard<std::mutex> lk(p->mu);
+    set_knob(p, p->adj_srole, mode);   // (drops the cached graphs when the value changes)
+    return 0;
+}
+
+int rdq_fwi_adjoint_role_info(rdq_fwi_plan *p, int32_t B, int32_t out[2])
+{
+    if (!p || !out || B < 1) return RDQ_E_INVALID;
+    std::lock_guard<std::mutex> lk(p->mu);
+    const int nwa = persistent_nw(p, B, true);
+    out[1] = nwa ? adjoint_role_pair(p, nwa, p->d_prof != nullptr) : -1;
+    out[0] = out[1] >= 0 ? 1 : 0;
+    return 0;
+}
+
+int rdq_fwi_role_row_pair(int32_t padded_row) { return padded_row < 0 ? RDQ_E_INVALID : role_row_pair(padded_row); }
 
 int rdq_fwi_wide_info(rdq_fwi_plan *p, int32_t B, int32_t out[4])
 {

@@ -160,18 +160,22 @@ class FwiPlan:
         12 / 8, 0 = chunked), 'fwd_T', 'adj_T', 'fwd_launches', 'adj_launches', 'fwd_overlap' /
         'adj_overlap' (the hand-off overlap mode that runs, set_handoff_overlap), 'fwd_roles' /
         'adj_roles' (the wave-role mode that runs, set_wave_roles), 'fwd_src_role' / 'adj_src_role' (the
-        source-role mode that runs, set_source_role)} of a
+        source-role mode that runs, set_source_role), 'adj_role' / 'adj_role_pair' (the adjoint-role mode that
+        runs, set_adjoint_role, and the row pair it runs with, -1 = none)} of a
         call with batch B (launches: time-loop kernel launches per call)."""
         out = (ctypes.c_int32 * 10)()
         _hip.check(self.lib.rdq_fwi_launch_info(self.handle, int(B), out), "rdq_fwi_launch_info")
         src = (ctypes.c_int32 * 2)()
         _hip.check(self.lib.rdq_fwi_source_role_info(self.handle, int(B), src), "rdq_fwi_source_role_info")
+        arole = (ctypes.c_int32 * 2)()
+        _hip.check(self.lib.rdq_fwi_adjoint_role_info(self.handle, int(B), arole), "rdq_fwi_adjoint_role_info")
         return {"fwd_persistent": bool(out[0]), "adj_persistent": bool(out[1]),
                 "fwd_class": int(out[0]), "adj_class": int(out[1]), "fwd_T": int(out[2]),
                 "adj_T": int(out[3]), "fwd_launches": int(out[4]), "adj_launches": int(out[5]),
                 "fwd_overlap": int(out[6]), "adj_overlap": int(out[7]),
                 "fwd_roles": int(out[8]), "adj_roles": int(out[9]),
-                "fwd_src_role": int(src[0]), "adj_src_role": int(src[1])}
+                "fwd_src_role": int(src[0]), "adj_src_role": int(src[1]),
+                "adj_role": int(arole[0]), "adj_role_pair": int(arole[1])}
 
     def set_sweep_delay(self, fwd_ticks, adj_ticks):
         """Persistent kernels: 10 ns ticks between an epoch's publish and its first hand-off pass."""
@@ -200,6 +204,21 @@ class FwiPlan:
         bit-identical in both modes."""
         _hip.check(self.lib.rdq_fwi_set_source_role(self.handle, int(fwd_mode), int(adj_mode)),
                    "rdq_fwi_set_source_role")
+
+    def set_adjoint_role(self, mode):
+        """Persistent (recurrence) adjoint, where the forward's source role would run and with wave roles on: 1
+        (default) = the wave that owns the source/receiver row runs every epoch but the last in a loop of its
+        own (the guard-free step plus the row's own work, the row's pair a compile-time constant of the kernel
+        the host picks), 0 = the generic loop.  launch_info reports the mode that runs.  Results are
+        bit-identical in both modes."""
+        _hip.check(self.lib.rdq_fwi_set_adjoint_role(self.handle, int(mode)), "rdq_fwi_set_adjoint_role")
+
+    def adjoint_role_waves(self):
+        """Waves that entered the adjoint's source/receiver loop in the last persistent adjoint call
+        (synchronises): one per workgroup whose interior rows own the source row; 0 where the role did not run."""
+        out = (ctypes.c_uint32 * 32)()
+        _hip.check(self.lib.rdq_fwi_debug_words(self.handle, out), "rdq_fwi_debug_words")
+        return int(out[24])
 
     def wide_info(self, B):
         """{'chains', 'fwd_spw', 'adj_spw', 'chain0_shots'}: the wide chunked kernels' concurrent launch

@@ -7,7 +7,8 @@ the first is the baseline) alternated N times each, event-timed per kernel: one 
 summary line with the bar a mode has to pass (every run faster than every baseline run, and the medians
 apart by at least three times the larger min-max spread).  --roles F,A sets the wave-role modes;
 --ab-knob roles makes --ab alternate wave-role mode pairs instead (e.g. --ab-modes "0,0;1,1"); --srole F,A sets
-the source-role modes and --ab-knob srole alternates those (e.g. --ab-modes "0,0;1,1")."""
+the source-role modes and --ab-knob srole alternates those (e.g. --ab-modes "0,0;1,1"); --arole M sets the
+adjoint's source/receiver role and --ab-knob arole alternates it (--ab-modes "0,0;0,1": the forward's half is 0)."""
 import argparse
 import json
 import os
@@ -35,9 +36,10 @@ ap.add_argument("--delay", default=None, help="pre-sweep delays of the persisten
 ap.add_argument("--overlap", default=None, help="hand-off overlap modes of the persistent kernels, 'fwd,adj'")
 ap.add_argument("--ab", type=int, default=0, help="rounds of an alternated A/B of hand-off overlap modes")
 ap.add_argument("--ab-modes", default="0,0;0,1", help="'fwd,adj' mode pairs of the A/B, baseline first")
-ap.add_argument("--ab-knob", default="overlap", choices=["overlap", "roles", "srole"], help="the setting --ab alternates")
+ap.add_argument("--ab-knob", default="overlap", choices=["overlap", "roles", "srole", "arole"], help="the setting --ab alternates")
 ap.add_argument("--roles", default=None, help="wave-role modes of the persistent kernels, 'fwd,adj'")
 ap.add_argument("--srole", default=None, help="source-role modes of the persistent kernels, 'fwd,adj'")
+ap.add_argument("--arole", type=int, default=None, help="source/receiver role of the persistent adjoint, 0 / 1")
 a = ap.parse_args()
 dev = torch.device("cuda:0")
 ctx = dict(n_grid=70, nt=a.nt, dx=10.0, dt=0.001, nbc=120, f=15.0, sz=10, gz=10, ng=70, ns=a.ns)
@@ -54,6 +56,8 @@ if a.roles:
     plan.set_wave_roles(*[int(x) for x in a.roles.split(",")])
 if a.srole:
     plan.set_source_role(*[int(x) for x in a.srole.split(",")])
+if a.arole is not None:
+    plan.set_adjoint_role(a.arole)
 sz = plan.sizes(a.B)
 dseis = torch.randn(a.B, a.ns, sz.nrec, plan.ng, device=dev)
 
@@ -84,13 +88,14 @@ if a.ab:
     pairs = [tuple(int(x) for x in m.split(",")) for m in a.ab_modes.split(";")]
     runs = {m: [] for m in pairs}
     timed(a.reps)                                         # warm-up (clocks, allocator), not recorded
-    setter = {"overlap": plan.set_handoff_overlap, "roles": plan.set_wave_roles, "srole": plan.set_source_role}[a.ab_knob]
-    key = "src_role" if a.ab_knob == "srole" else a.ab_knob
+    setter = {"overlap": plan.set_handoff_overlap, "roles": plan.set_wave_roles, "srole": plan.set_source_role,
+              "arole": lambda f, m: plan.set_adjoint_role(m)}[a.ab_knob]   # (the adjoint's alone: the forward's half is 0)
+    key = {"srole": "src_role", "arole": "role"}.get(a.ab_knob, a.ab_knob)
     for rnd in range(a.ab):
         for m in pairs:
             setter(*m)
             info = plan.launch_info(a.B)
-            assert (info[f"fwd_{key}"], info[f"adj_{key}"]) == m, info
+            assert (info.get(f"fwd_{key}", 0), info[f"adj_{key}"]) == m, info
             fw, ad = timed(a.reps)
             runs[m].append((fw, ad))
             print(json.dumps({"round": rnd, a.ab_knob: list(m), "fwd_ms": round(fw, 4), "adj_ms": round(ad, 4)}),
@@ -139,6 +144,7 @@ for T, G in cfgs:
                 "overlap": [plan.launch_info(a.B)["fwd_overlap"], plan.launch_info(a.B)["adj_overlap"]],
                 "roles": [plan.launch_info(a.B).get("fwd_roles", 0), plan.launch_info(a.B).get("adj_roles", 0)],
                 "srole": [plan.launch_info(a.B).get("fwd_src_role", 0), plan.launch_info(a.B).get("adj_src_role", 0)],
+                "arole": [plan.launch_info(a.B).get("adj_role", 0), plan.launch_info(a.B).get("adj_role_pair", -1)],
                 "fwd_launches": plan.launch_info(a.B)["fwd_launches"], "fwd_ms": round(fw, 3), "adj_ms": round(ad, 3),
                 "shot_ts_per_s": round(a.ns * a.nt * a.B / ((fw + ad) * 1e-3))})
     if a.profile and G:
