@@ -53,7 +53,8 @@ typedef struct rdq_fwi_geom {
     int32_t isz, igz;          /* source / receiver row on the padded grid */
     const int32_t *isx;        /* host [ns] source columns (padded grid) */
     const int32_t *igx;        /* host [ng] receiver columns (padded grid) */
-    const double *wavelet;     /* host [nt] Ricker wavelet (pde.py:26-36), fp64 */
+    const double *wavelet;     /* host [nt] source wavelet, fp64, shared by every shot: the Ricker wavelet
+                                  (pde.py:26-36) or any other signature; cast to fp32 by the plan */
 } rdq_fwi_geom;
 
 typedef struct rdq_fwi_plan rdq_fwi_plan;
@@ -391,6 +392,45 @@ int rdq_fwi_born(const rdq_fwi_plan *plan, int32_t B, const float *coeffs, const
 int rdq_fwi_born_fused(const rdq_fwi_plan *plan, int32_t B, int32_t K, const float *coeffs,
                        const float *dwork, float *seis, float *dseis_out, float *ckpt, float *ring,
                        hipStream_t stream);
+
+/* Caller-supplied source wavelets, per model and per shot, and their gradient: K1 / K2 and their checkpointed
+ * forms with the samples read from device memory instead of the plan's wavelet (rdq_fwi_geom.wavelet).
+ *   Equations.  The forward step as written above (rdq_fwi_born) with w[n] replaced by the call's own sample,
+ *     P_{n+1}[b, s, isz, isx[s]] += beta[b, isz, isx[s]] * w[b, s, n],   n = 0 .. nt - 1,
+ *   w[b, s, n] = wav[b * model_stride + s * shot_stride + n] (s is the plan's own shot index), in the chunked
+ *   forward's fp32 order (add = beta * w; P = P + add).  The seismograms are linear in w.  With L_k the adjoint field
+ *   of P_k (K2), taken after step k's receiver residual has been added (where K2 reads it for gbeta), the transpose is
+ *     gwav[b, s, k - 1] = L_k[b, s, isz, isx[s]] * beta[b, isz, isx[s]]      (one fp32 multiply),
+ *   and gbeta[b, s] = sum_k L_k(src) w[b, s, k - 1] as before, with the loaded sample.  A wavelet shared between
+ *   shots or models (a zero stride) receives the sum of gwav over the shared axes, which is the caller's to take.
+ *   One writer per element.  The narrow kernels' tile interiors partition the padded grid, so exactly one lane of one
+ *   workgroup owns a shot's source cell, and a call runs every step k once (a checkpointed call: once in the
+ *   segment that holds it).  Every gwav element is therefore written exactly once per call, with a plain store: no
+ *   atomics, no dependence on what the buffer held (it is overwritten, not accumulated), one fixed result.
+ *   These calls always run the narrow chunked kernels at rdq_fwi_set_tuning's depths and chains, whatever
+ *   rdq_fwi_set_persistent or RDQ_VARIANT_NARROW_CHUNKED say (RDQ_VARIANT_FWD_GEN chooses the forward's coefficient
+ *   source), stream-ordered on caller-owned buffers under the one-call-in-flight rule.  The other arguments are
+ *   those of the call each one mirrors; a checkpointed backward's recompute reads the same device wavelets, so they
+ *   must be unchanged between the two calls.  seis, gwav, gA and gbeta are bit-identical for every depth, chain
+ *   count, graph setting and K, and with the plan's own wavelet passed as (wav, 0, 0) seis, gA and gbeta are those
+ *   of the plain calls on the narrow chunked kernels.  RDQ_E_INVALID for a null `src` or `wav`, B < 1 or a
+ *   negative stride. */
+typedef struct rdq_fwi_source {
+    const float *wav;                    /* device, fp32: sample n of model b, shot s at wav[b*model_stride + s*shot_stride + n] */
+    int64_t model_stride, shot_stride;   /* in floats; 0 = shared by all models / all shots */
+    float *gwav;                         /* adjoint calls only: float [B][ns][nt] = d(loss)/d(w[b, s, :]), overwritten;
+                                            NULL = not wanted */
+} rdq_fwi_source;
+int rdq_fwi_forward_src(const rdq_fwi_plan *plan, int32_t B, const float *coeffs, const rdq_fwi_source *src,
+                        float *seis, float *history, float *ring, hipStream_t stream);
+int rdq_fwi_adjoint_src(const rdq_fwi_plan *plan, int32_t B, const float *coeffs, const rdq_fwi_source *src,
+                        const float *history, const float *dseis, float *ring, float *gA, double *gk_part,
+                        float *gbeta, hipStream_t stream);
+int rdq_fwi_forward_ckpt_src(const rdq_fwi_plan *plan, int32_t B, int32_t K, const float *coeffs,
+                             const rdq_fwi_source *src, float *seis, float *ckpt, float *ring, hipStream_t stream);
+int rdq_fwi_adjoint_ckpt_src(const rdq_fwi_plan *plan, int32_t B, int32_t K, const float *coeffs,
+                             const rdq_fwi_source *src, const float *ckpt, float *seg, const float *dseis,
+                             float *ring, float *gA, double *gk_part, float *gbeta, hipStream_t stream);
 
 /* K4: d(loss)/d(v) [B][nz][nx] (contiguous) from the accumulators: chain through
  * alpha/beta/sponge(vmin), replicate-pad fold, and (RDQ_VEL_NORMALIZED) the x1500 of the

@@ -297,6 +297,10 @@ struct FwdTBArgs {
     float w[FWD_W_MAX];                  // wavelet samples w[n0 .. n0+nsteps-1]
     int hbase;                           // virtual slot held by hist's first level (0: the whole history;
                                          // a checkpointed segment's buffer starts at its first boundary)
+    // SRC instantiations (rdq_fwi_*_src): the call's own wavelets, sample n of model b, shot s at
+    // wav[b * wms + s * wss + n] (strides in floats, 0 = shared); `w` is not read
+    const float *wav;
+    long long wms, wss;
 };
 
 // exchange two boundary rows each way between the NW waves of the workgroup
@@ -489,7 +493,10 @@ __device__ __forceinline__ int wrapn(int v, int n)
     return v;
 }
 
-template <int T, bool GEN>
+// SRC: the source samples are the call's own wavelets, read from a.wav (rdq_fwi_*_src) instead of the
+// kernel-argument samples a.w of the plan's wavelet; b and s are workgroup-uniform, so the launch's T
+// samples are uniform loads, hoisted ahead of the step loop.  Same operation order either way.
+template <int T, bool GEN, bool SRC = false>
 __global__ __launch_bounds__(64 * TB_NW) void k_fwd_tb(FwdTBArgs a)
 {
     constexpr int H = 2 * T, IW = 64 - 2 * H, IH = TB_RH - 2 * H;
@@ -542,6 +549,13 @@ __global__ __launch_bounds__(64 * TB_NW) void k_fwd_tb(FwdTBArgs a)
     const int rcv0 = rs < re ? g.rcv_list[rs] : -1;
     const bool rmulti = __any(re - rs > 1);               // wave-uniform: a column with several receivers
     (void)srow;
+    float ws[T];                    // SRC: w[b, s, n0 .. n0 + nsteps - 1]
+    if constexpr (SRC) {
+        const float *wp = a.wav + (size_t)b * a.wms + (size_t)s * a.wss + a.n0;
+#pragma unroll
+        for (int t = 0; t < T; ++t) ws[t] = t < a.nsteps ? wp[t] : 0.0f;
+    }
+    (void)ws;
 #pragma unroll
     for (int t = 0; t < T; ++t) {
         if (t >= a.nsteps) break;
@@ -565,7 +579,11 @@ __global__ __launch_bounds__(64 * TB_NW) void k_fwd_tb(FwdTBArgs a)
         if (smask) {                                                   // pde.py:80-81
 #pragma unroll
             for (int r = 0; r < TB_R; ++r)
-                if ((smask & (1u << r)) && scol) { const float add = bsrc * a.w[t]; prv[r] = prv[r] + add; }
+                if ((smask & (1u << r)) && scol) {
+                    float wt;
+                    if constexpr (SRC) wt = ws[t]; else wt = a.w[t];
+                    const float add = bsrc * wt; prv[r] = prv[r] + add;
+                }
         }
         const int n = a.n0 + t;
         if (a.hist && xin) {
@@ -613,6 +631,12 @@ struct AdjTBArgs {
     int spw, ns_sh;                      // wide kernels: shots per workgroup, shots of the launch's chain
     float w[ADJ_W_MAX];                  // w[k0-1-t], t < nsteps (narrow: <= TB_MAXT, wide: <= TW_ADJ_MAXT steps)
     int hbase;                           // virtual slot held by hist's first level (FwdTBArgs::hbase)
+    // SRC instantiations (rdq_fwi_*_src): the call's own wavelets as FwdTBArgs::wav (`w` is not read), and
+    // gwav [B][ns][nt] = d(loss)/d(wav), one plain store per shot-step (nullptr: not wanted)
+    const float *wav;
+    long long wms, wss;
+    float *gwav;
+    int nt;
 };
 
 // Adjoint with the same register-region blocking, walking k = k0, k0-1, ...:
@@ -620,7 +644,13 @@ struct AdjTBArgs {
 // and, on the interior only, the per-shot accumulators (loaded once, stored once per launch):
 //   gA_s += L_k (2c1 P_{k-1} + c2 S1(P_{k-1}) + c3 S2(P_{k-1})),  gk += (K P_{k-1})(L_{k+1} - L_k),
 //   gbeta[s] += L_k(src) w[k-1].
-template <int T>
+// SRC: w is the call's own wavelet of (b, s), loaded from a.wav (uniform loads, hoisted), and the transpose
+// of the source injection P_k(src) += beta(src) w[b, s, k-1] is
+//   gwav[b, s, k-1] = L_k(src) beta(src):   one fp32 multiply, L_k taken after step k's receiver residual,
+// stored by the lane that owns the source cell (gbl).  The tiles' interiors partition the grid, so exactly one
+// lane of one workgroup owns that cell, and a call runs every k once: one writer per element, a plain store,
+// no atomics and no dependence on what gwav held.
+template <int T, bool SRC = false>
 __global__ __launch_bounds__(64 * TB_NW, 4) void k_adj_tb(AdjTBArgs a)
 {
     constexpr int H = 2 * T, IW = 64 - 2 * H, IH = TB_RH - 2 * H;
@@ -669,6 +699,17 @@ __global__ __launch_bounds__(64 * TB_NW, 4) void k_adj_tb(AdjTBArgs a)
     // per-step read-modify-write of a.gbeta[bs]), stored once at the end
     const bool gbl = (smask & rin) && scol && xin;       // the source cell is this lane's own cell
     float gbacc = gbl ? a.gbeta[bs] : 0.0f;
+    float ws[T];                    // SRC: w[b, s, k0 - 1 - t]
+    float bsrc = 0.0f;              // SRC: beta at the source cell, on the lane that owns it and stores gwav
+    bool gw = false;
+    if constexpr (SRC) {
+        const float *wp = a.wav + (size_t)b * a.wms + (size_t)s * a.wss + a.k0 - 1;
+#pragma unroll
+        for (int t = 0; t < T; ++t) ws[t] = t < a.nsteps ? wp[-t] : 0.0f;
+        gw = gbl && a.gwav;
+        if (gw) bsrc = a.coeffs[4 * g.cstride + (size_t)b * g.slice + (size_t)g.isz * g.ld + isx];
+    }
+    (void)ws; (void)bsrc; (void)gw;
     double ksum = 0.0;
     // history P_{k-1} on the rows whose stencil the interior needs: HBM stream, prefetched one
     // step ahead so its latency hides under the previous step
@@ -746,7 +787,19 @@ __global__ __launch_bounds__(64 * TB_NW, 4) void k_adj_tb(AdjTBArgs a)
                 ga = ga + c;
                 float kk = kal[r] * pc; const float dl = cur[r] - l; kk = kk * dl;  // fp32 term,
                 ksum += (double)kk;                                                             // fp64 sum
-                if ((smask & (1u << r)) && scol) { const float gb = l * a.w[t]; gbacc = gbacc + gb; }
+                if ((smask & (1u << r)) && scol) {
+                    float wt;
+                    if constexpr (SRC) wt = ws[t]; else wt = a.w[t];
+                    const float gb = l * wt; gbacc = gbacc + gb;
+                }
+            }
+        }
+        if constexpr (SRC) {   // one store per step, not one per row: the source row's L_k picked by the wave-uniform mask
+            if (gw) {
+                float ls = 0.0f;
+#pragma unroll
+                for (int r = 0; r < TB_R; ++r) if (smask & rin & (1u << r)) ls = prv[r];
+                a.gwav[(size_t)bs * a.nt + (k - 1)] = ls * bsrc;
             }
         }
     }
@@ -3334,10 +3387,11 @@ __global__ __launch_bounds__(256) void k_smooth_bwd(int kind, int H, int W, cons
 // ======================================================================================= plan
 struct GraphEntry {
     int kind;                 // 0 fwd-history, 1 fwd-ring, 2 adjoint, 3 fwd-checkpoint, 4 adjoint-checkpoint, 5 born,
-                              // 6 fused forward + born
+                              // 6 fused forward + born; + 8: the same pass with the call's own wavelets
     int B;
     int K;                    // checkpoint interval (kinds 3, 4, 6; else 0): it shapes the launch sequence
-    const void *ptrs[8];
+    const void *ptrs[10];     // the call's buffers; a per-call source adds its wav and gwav
+    long long strides[2];     // and its two wavelet strides (else 0)
     hipGraphExec_t exec;
     uint64_t last_use;
 };
@@ -3632,6 +3686,17 @@ KernelRef<FwdTBArgs> fwd_tb_kernel(int T, bool gen)
 KernelRef<AdjTBArgs> adj_tb_kernel(int T)
 {
     return with_depth<TB_MAXT>(T, [](auto t) -> KernelRef<AdjTBArgs> { return {k_adj_tb<t()>, 64 * TB_NW}; });
+}
+// the same two with the call's own wavelets (rdq_fwi_*_src)
+KernelRef<FwdTBArgs> fwd_tb_src_kernel(int T, bool gen)
+{
+    return with_depth<TB_MAXT>(T, [&](auto t) -> KernelRef<FwdTBArgs> {
+        return {gen ? k_fwd_tb<t(), true, true> : k_fwd_tb<t(), false, true>, 64 * TB_NW};
+    });
+}
+KernelRef<AdjTBArgs> adj_tb_src_kernel(int T)
+{
+    return with_depth<TB_MAXT>(T, [](auto t) -> KernelRef<AdjTBArgs> { return {k_adj_tb<t(), true>, 64 * TB_NW}; });
 }
 KernelRef<BornTBArgs> born_tb_kernel(int T, bool gen)
 {
@@ -4111,6 +4176,9 @@ __global__ __launch_bounds__(256) void k_ckpt_levels(const float *src, float *ds
 //             launch ending on an interior boundary writes its pair into the checkpoint store and the next reads
 //             it there); the dP pair (in2 / out2) always ping-pongs in ring levels 4-7.  Narrow kernels at the
 //             forward's narrow depth and chains, as born.
+// A call with its own wavelets (`src`: rdq_fwi_*_src) runs the same four passes on the narrow kernels' SRC
+// instantiations at the narrow depths and chains, as born does; the wavelet and gwav indices are absolute, so a
+// segment's recompute reads the samples the first pass read.
 // The adjoint's levels stay in the ring between launches and the ring parity runs on across segments.
 // Every launch of a chain is ordered on the chain's stream, so a segment's recompute overwrites the
 // segment buffer only after the previous segment's adjoint has read it.
@@ -4134,10 +4202,11 @@ struct Launch {
 // passes that always run the narrow (64-column) kernels at the forward's narrow depth
 bool narrow_pass(Pass pass) { return pass == Pass::born || pass == Pass::fwd_born; }
 
-std::vector<Launch> chunked_schedule(const rdq_fwi_plan *p, int B, Pass pass, const CkptPlan &cp)
+std::vector<Launch> chunked_schedule(const rdq_fwi_plan *p, int B, Pass pass, const CkptPlan &cp, bool src = false)
 {
-    const bool wide = p->wide && !narrow_pass(pass);
-    const int Tf = wide ? wide_fwd_depth(p) : p->fwd_T, Ta = chunk_depth(p, true), S = chain_count(p, wide), ns = p->g.ns;
+    const bool wide = p->wide && !narrow_pass(pass) && !src;
+    const int Tf = wide ? wide_fwd_depth(p) : p->fwd_T, Ta = wide ? wide_adj_depth(p) : p->adj_T;
+    const int S = chain_count(p, wide), ns = p->g.ns;
     std::vector<Launch> sched;
     auto add = [&](Launch::Kind kind, int c, int sg, int first, int nsteps, LevelPair in, LevelPair out) {
         Launch l{};
@@ -4216,18 +4285,20 @@ struct ChunkBufs {
     float *gbeta;
     const float *dwork;              // born: the perturbation workspace (`seis` is then the linearised record)
     float *dseis_out;                // fwd_born: the linearised record (`seis` is the forward's)
+    const rdq_fwi_source *src;       // the call's own wavelets (rdq_fwi_*_src), or nullptr: the plan's
 };
 
 int enqueue_chunked(rdq_fwi_plan *p, int B, Pass pass, int K, const ChunkBufs &b, hipStream_t st)
 {
-    const std::vector<Launch> sched = chunked_schedule(p, B, pass, ckpt_plan(p, K));
+    const bool src = b.src != nullptr;
+    const std::vector<Launch> sched = chunked_schedule(p, B, pass, ckpt_plan(p, K), src);
     FwdTBArgs f{};
     AdjTBArgs a{};
     BornTBArgs d{};
     FwdBornTBArgs u{};
     f.g = a.g = d.g = u.g = tb_geo(p, B);
     const size_t L = a.g.level, slice = a.g.slice;
-    const int S = chain_count(p, p->wide && !narrow_pass(pass)), ns = p->g.ns, nblk_alloc = gk_blocks(p);
+    const int S = chain_count(p, p->wide && !narrow_pass(pass) && !src), ns = p->g.ns, nblk_alloc = gk_blocks(p);
     const bool adjoint = pass == Pass::adj_hist || pass == Pass::adj_ckpt;
     if (adjoint) {   // the gk_part one-writer invariant, on every adjoint launch, before anything is enqueued
         GkWriters writers((size_t)B * ns, nblk_alloc);
@@ -4255,6 +4326,11 @@ int enqueue_chunked(rdq_fwi_plan *p, int B, Pass pass, int K, const ChunkBufs &b
     f.seis = b.seis; f.hist = b.hist;
     a.hist = b.hist; a.dseis = b.dseis; a.gA = b.gA; a.gk_part = b.gk; a.gbeta = b.gbeta;
     a.nblk = nblk_alloc;
+    if (src) {
+        f.wav = a.wav = b.src->wav;
+        f.wms = a.wms = b.src->model_stride; f.wss = a.wss = b.src->shot_stride;
+        a.gwav = b.src->gwav; a.nt = p->g.nt;
+    }
     auto level = [&](LevelPair lp, int j) -> float * {
         float *base = lp.store == Store::ring ? b.ring : lp.store == Store::ckpt ? b.ckpt
                       : lp.store == Store::hist ? b.hist : nullptr;
@@ -4275,7 +4351,7 @@ int enqueue_chunked(rdq_fwi_plan *p, int B, Pass pass, int K, const ChunkBufs &b
             for (int t = 0; t < FWD_W_MAX; ++t) f.w[t] = t < l.nsteps ? p->wavf[l.first + t] : 0.0f;
             f.in_prev = level(l.in, 0); f.in_cur = level(l.in, 1);
             f.out_prev = level(l.out, 0); f.out_cur = level(l.out, 1);
-            launch_kernel(chunk_fwd_kernel(p, l.nsteps), l.grid, cs, f);
+            launch_kernel(src ? fwd_tb_src_kernel(p->fwd_T, p->fwd_gen) : chunk_fwd_kernel(p, l.nsteps), l.grid, cs, f);
         } else if (l.kind == Launch::born) {
             d.g.s_off = l.s_off; d.g.ns_grp = l.ns_grp; d.g.tiles_x = l.tiles_x; d.g.ntiles = l.ntiles;
             d.n0 = l.first; d.nsteps = l.nsteps;
@@ -4299,7 +4375,7 @@ int enqueue_chunked(rdq_fwi_plan *p, int B, Pass pass, int K, const ChunkBufs &b
             for (int t = 0; t < ADJ_W_MAX; ++t) a.w[t] = t < l.nsteps ? p->wavf[l.first - 1 - t] : 0.0f;
             a.in_l1 = level(l.in, 0); a.in_l2 = level(l.in, 1);
             a.out_l1 = level(l.out, 0); a.out_l2 = level(l.out, 1);
-            launch_kernel(chunk_adj_kernel(p, l.nsteps), l.grid, cs, a);
+            launch_kernel(src ? adj_tb_src_kernel(p->adj_T) : chunk_adj_kernel(p, l.nsteps), l.grid, cs, a);
         }
     }
     RDQ_CHECK(hipGetLastError());
@@ -4341,14 +4417,16 @@ int fold_residuals(const rdq_fwi_plan *p, int B, const float *&dseis, float *rin
 
 template <class F>
 int run_cached(rdq_fwi_plan *p, int kind, int B, std::initializer_list<const void *> key, hipStream_t st, F &&launch,
-               int K = 0)
+               int K = 0, const rdq_fwi_source *src = nullptr)
 {
     if (!p->graphs) return launch(st);
-    const void *k[8] = {nullptr};
+    const void *k[10] = {nullptr};
+    long long ks[2] = {0, 0};
     int n = 0;
     for (const void *v : key) k[n++] = v;
+    if (src) { k[8] = src->wav; k[9] = src->gwav; ks[0] = src->model_stride; ks[1] = src->shot_stride; }
     for (auto &e : p->cache)
-        if (e.kind == kind && e.B == B && e.K == K && std::equal(k, k + 8, e.ptrs)) {
+        if (e.kind == kind && e.B == B && e.K == K && std::equal(k, k + 10, e.ptrs) && std::equal(ks, ks + 2, e.strides)) {
             e.last_use = ++p->tick;
             RDQ_CHECK(hipGraphLaunch(e.exec, st));
             return 0;
@@ -4362,7 +4440,8 @@ int run_cached(rdq_fwi_plan *p, int kind, int B, std::initializer_list<const voi
     RDQ_CHECK(ee);
     GraphEntry e{};
     e.kind = kind; e.B = B; e.K = K;
-    std::copy(k, k + 8, e.ptrs);
+    std::copy(k, k + 10, e.ptrs);
+    std::copy(ks, ks + 2, e.strides);
     const hipError_t ie = hipGraphInstantiate(&e.exec, graph, nullptr, nullptr, 0);
     (void)hipGraphDestroy(graph);
     RDQ_CHECK(ie);
@@ -4814,15 +4893,21 @@ int rdq_fwi_coeffs(const rdq_fwi_plan *p, int32_t B, const float *vn, const int6
     return 0;
 }
 
-int rdq_fwi_forward(const rdq_fwi_plan *pc, int32_t B, const float *coeffs, float *seis, float *hist,
-                    float *ring, hipStream_t st)
+// a call's source: usable (a wavelet, strides >= 0), or absent (nullptr: the plan's wavelet)
+static bool source_ok(const rdq_fwi_source *src)
 {
-    rdq_fwi_plan *p = const_cast<rdq_fwi_plan *>(pc);
+    return src && src->wav && src->model_stride >= 0 && src->shot_stride >= 0;
+}
+
+// K1, with the plan's wavelet (src == nullptr) or the call's own (always the narrow chunked kernels)
+static int forward_call(rdq_fwi_plan *p, int32_t B, const float *coeffs, const rdq_fwi_source *src, float *seis,
+                        float *hist, float *ring, hipStream_t st)
+{
     if (!p || !coeffs || !seis || (!hist && !ring) || B < 1) return RDQ_E_INVALID;
     std::lock_guard<std::mutex> lk(p->mu);
     RDQ_TRY(plan_enter(p, st));
     int per = 0;
-    if (const int nw = persistent_nw(p, B, false, &per)) {
+    if (const int nw = src ? 0 : persistent_nw(p, B, false, &per)) {
         if (!ring) return RDQ_E_INVALID;   // the persistent kernel's hand-off granules live in `ring`
         // direct launch (one kernel + memsets per shot group: nothing for a graph to amortise; the
         // arrival counters of pt_assign are zeroed by a stream-ordered memset right before it)
@@ -4830,28 +4915,55 @@ int rdq_fwi_forward(const rdq_fwi_plan *pc, int32_t B, const float *coeffs, floa
     }
     // chunked: the store-all schedule, writing the history or (no-grad) ping-ponging in the ring
     ChunkBufs b{};
-    b.coeffs = coeffs; b.seis = seis; b.hist = hist; b.ring = ring;
-    return run_cached(p, hist ? 0 : 1, B, {coeffs, seis, hist, ring}, st, [&](hipStream_t s) {
+    b.coeffs = coeffs; b.seis = seis; b.hist = hist; b.ring = ring; b.src = src;
+    return run_cached(p, (hist ? 0 : 1) + (src ? 8 : 0), B, {coeffs, seis, hist, ring}, st, [&](hipStream_t s) {
         return enqueue_chunked(p, B, hist ? Pass::fwd_hist : Pass::fwd_ring, p->g.nt, b, s);
-    });
+    }, 0, src);
 }
 
-int rdq_fwi_adjoint(const rdq_fwi_plan *pc, int32_t B, const float *coeffs, const float *hist,
-                    const float *dseis, float *ring, float *gA, double *gk, float *gbeta, hipStream_t st)
+int rdq_fwi_forward(const rdq_fwi_plan *pc, int32_t B, const float *coeffs, float *seis, float *hist,
+                    float *ring, hipStream_t st)
 {
-    rdq_fwi_plan *p = const_cast<rdq_fwi_plan *>(pc);
+    return forward_call(const_cast<rdq_fwi_plan *>(pc), B, coeffs, nullptr, seis, hist, ring, st);
+}
+
+int rdq_fwi_forward_src(const rdq_fwi_plan *pc, int32_t B, const float *coeffs, const rdq_fwi_source *src,
+                        float *seis, float *hist, float *ring, hipStream_t st)
+{
+    if (!source_ok(src)) return RDQ_E_INVALID;
+    return forward_call(const_cast<rdq_fwi_plan *>(pc), B, coeffs, src, seis, hist, ring, st);
+}
+
+static int adjoint_call(rdq_fwi_plan *p, int32_t B, const float *coeffs, const rdq_fwi_source *src,
+                        const float *hist, const float *dseis, float *ring, float *gA, double *gk, float *gbeta,
+                        hipStream_t st)
+{
     if (!p || !coeffs || !hist || !dseis || !ring || !gA || !gk || !gbeta || B < 1) return RDQ_E_INVALID;
     std::lock_guard<std::mutex> lk(p->mu);
     RDQ_TRY(plan_enter(p, st));
     RDQ_TRY(fold_residuals(p, B, dseis, ring, st));
     int per = 0;
-    if (const int nw = persistent_nw(p, B, true, &per))
+    if (const int nw = src ? 0 : persistent_nw(p, B, true, &per))
         return launch_adjoint_pt(p, B, nw, per, coeffs, hist, dseis, ring, gA, gk, gbeta, st);
     ChunkBufs b{};
     b.coeffs = coeffs; b.hist = const_cast<float *>(hist); b.ring = ring; b.dseis = dseis;
-    b.gA = gA; b.gk = gk; b.gbeta = gbeta;
-    return run_cached(p, 2, B, {coeffs, hist, dseis, ring, gA, gk, gbeta}, st,
-                      [&](hipStream_t s) { return enqueue_chunked(p, B, Pass::adj_hist, p->g.nt, b, s); });
+    b.gA = gA; b.gk = gk; b.gbeta = gbeta; b.src = src;
+    return run_cached(p, 2 + (src ? 8 : 0), B, {coeffs, hist, dseis, ring, gA, gk, gbeta}, st,
+                      [&](hipStream_t s) { return enqueue_chunked(p, B, Pass::adj_hist, p->g.nt, b, s); }, 0, src);
+}
+
+int rdq_fwi_adjoint(const rdq_fwi_plan *pc, int32_t B, const float *coeffs, const float *hist,
+                    const float *dseis, float *ring, float *gA, double *gk, float *gbeta, hipStream_t st)
+{
+    return adjoint_call(const_cast<rdq_fwi_plan *>(pc), B, coeffs, nullptr, hist, dseis, ring, gA, gk, gbeta, st);
+}
+
+int rdq_fwi_adjoint_src(const rdq_fwi_plan *pc, int32_t B, const float *coeffs, const rdq_fwi_source *src,
+                        const float *hist, const float *dseis, float *ring, float *gA, double *gk, float *gbeta,
+                        hipStream_t st)
+{
+    if (!source_ok(src)) return RDQ_E_INVALID;
+    return adjoint_call(const_cast<rdq_fwi_plan *>(pc), B, coeffs, src, hist, dseis, ring, gA, gk, gbeta, st);
 }
 
 // perturbation workspace: dam [B][nz][nx], ratio [B], dbeta [B][ns], oscale [B], dmax [B] (k_dcoeffs)
@@ -4940,25 +5052,37 @@ int rdq_fwi_ckpt_info(rdq_fwi_plan *p, int32_t B, int32_t K, int32_t out[4])
     return 0;
 }
 
-int rdq_fwi_forward_ckpt(const rdq_fwi_plan *pc, int32_t B, int32_t K, const float *coeffs, float *seis,
-                         float *ckpt, float *ring, hipStream_t st)
+static int forward_ckpt_call(rdq_fwi_plan *p, int32_t B, int32_t K, const float *coeffs, const rdq_fwi_source *src,
+                             float *seis, float *ckpt, float *ring, hipStream_t st)
 {
-    rdq_fwi_plan *p = const_cast<rdq_fwi_plan *>(pc);
     if (!p || !coeffs || !seis || !ring || B < 1 || K < 1) return RDQ_E_INVALID;
     if (!ckpt && ckpt_plan(p, K).nseg > 1) return RDQ_E_INVALID;
     std::lock_guard<std::mutex> lk(p->mu);
     RDQ_TRY(plan_enter(p, st));
     ChunkBufs b{};
-    b.coeffs = coeffs; b.seis = seis; b.ckpt = ckpt; b.ring = ring;
-    return run_cached(p, 3, B, {coeffs, seis, ckpt, ring}, st,
-                      [&](hipStream_t s) { return enqueue_chunked(p, B, Pass::fwd_ring, K, b, s); }, ckpt_plan(p, K).K);
+    b.coeffs = coeffs; b.seis = seis; b.ckpt = ckpt; b.ring = ring; b.src = src;
+    return run_cached(p, 3 + (src ? 8 : 0), B, {coeffs, seis, ckpt, ring}, st,
+                      [&](hipStream_t s) { return enqueue_chunked(p, B, Pass::fwd_ring, K, b, s); }, ckpt_plan(p, K).K,
+                      src);
 }
 
-int rdq_fwi_adjoint_ckpt(const rdq_fwi_plan *pc, int32_t B, int32_t K, const float *coeffs, const float *ckpt,
-                         float *seg, const float *dseis, float *ring, float *gA, double *gk, float *gbeta,
-                         hipStream_t st)
+int rdq_fwi_forward_ckpt(const rdq_fwi_plan *pc, int32_t B, int32_t K, const float *coeffs, float *seis,
+                         float *ckpt, float *ring, hipStream_t st)
 {
-    rdq_fwi_plan *p = const_cast<rdq_fwi_plan *>(pc);
+    return forward_ckpt_call(const_cast<rdq_fwi_plan *>(pc), B, K, coeffs, nullptr, seis, ckpt, ring, st);
+}
+
+int rdq_fwi_forward_ckpt_src(const rdq_fwi_plan *pc, int32_t B, int32_t K, const float *coeffs,
+                             const rdq_fwi_source *src, float *seis, float *ckpt, float *ring, hipStream_t st)
+{
+    if (!source_ok(src)) return RDQ_E_INVALID;
+    return forward_ckpt_call(const_cast<rdq_fwi_plan *>(pc), B, K, coeffs, src, seis, ckpt, ring, st);
+}
+
+static int adjoint_ckpt_call(rdq_fwi_plan *p, int32_t B, int32_t K, const float *coeffs, const rdq_fwi_source *src,
+                             const float *ckpt, float *seg, const float *dseis, float *ring, float *gA, double *gk,
+                             float *gbeta, hipStream_t st)
+{
     if (!p || !coeffs || !seg || !dseis || !ring || !gA || !gk || !gbeta || B < 1 || K < 1) return RDQ_E_INVALID;
     if (!ckpt && ckpt_plan(p, K).nseg > 1) return RDQ_E_INVALID;
     std::lock_guard<std::mutex> lk(p->mu);
@@ -4966,9 +5090,27 @@ int rdq_fwi_adjoint_ckpt(const rdq_fwi_plan *pc, int32_t B, int32_t K, const flo
     RDQ_TRY(fold_residuals(p, B, dseis, ring, st));
     ChunkBufs b{};
     b.coeffs = coeffs; b.hist = seg; b.ckpt = const_cast<float *>(ckpt); b.ring = ring; b.dseis = dseis;
-    b.gA = gA; b.gk = gk; b.gbeta = gbeta;
-    return run_cached(p, 4, B, {coeffs, ckpt, seg, dseis, ring, gA, gk, gbeta}, st,
-                      [&](hipStream_t s) { return enqueue_chunked(p, B, Pass::adj_ckpt, K, b, s); }, ckpt_plan(p, K).K);
+    b.gA = gA; b.gk = gk; b.gbeta = gbeta; b.src = src;
+    return run_cached(p, 4 + (src ? 8 : 0), B, {coeffs, ckpt, seg, dseis, ring, gA, gk, gbeta}, st,
+                      [&](hipStream_t s) { return enqueue_chunked(p, B, Pass::adj_ckpt, K, b, s); }, ckpt_plan(p, K).K,
+                      src);
+}
+
+int rdq_fwi_adjoint_ckpt(const rdq_fwi_plan *pc, int32_t B, int32_t K, const float *coeffs, const float *ckpt,
+                         float *seg, const float *dseis, float *ring, float *gA, double *gk, float *gbeta,
+                         hipStream_t st)
+{
+    return adjoint_ckpt_call(const_cast<rdq_fwi_plan *>(pc), B, K, coeffs, nullptr, ckpt, seg, dseis, ring, gA, gk,
+                             gbeta, st);
+}
+
+int rdq_fwi_adjoint_ckpt_src(const rdq_fwi_plan *pc, int32_t B, int32_t K, const float *coeffs,
+                             const rdq_fwi_source *src, const float *ckpt, float *seg, const float *dseis, float *ring,
+                             float *gA, double *gk, float *gbeta, hipStream_t st)
+{
+    if (!source_ok(src)) return RDQ_E_INVALID;
+    return adjoint_ckpt_call(const_cast<rdq_fwi_plan *>(pc), B, K, coeffs, src, ckpt, seg, dseis, ring, gA, gk, gbeta,
+                             st);
 }
 
 int rdq_fwi_grad_finalize(const rdq_fwi_plan *p, int32_t B, const float *coeffs, const void *vstat,

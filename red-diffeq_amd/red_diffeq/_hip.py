@@ -39,6 +39,11 @@ class FwiCkptSizes(ctypes.Structure):
     _fields_ = [("nseg", c_int32), ("seg_levels", c_int32), ("ckpt", c_size_t), ("seg", c_size_t)]
 
 
+class FwiSource(ctypes.Structure):
+    """struct rdq_fwi_source."""
+    _fields_ = [("wav", c_void_p), ("model_stride", c_int64), ("shot_stride", c_int64), ("gwav", c_void_p)]
+
+
 class ConvDesc(ctypes.Structure):
     """struct rdq_conv_desc."""
     _fields_ = [(n, c_int32) for n in ("B", "cin1", "cin2", "H", "W", "cout", "kh", "kw", "pad", "in_mode")]
@@ -92,6 +97,14 @@ SIGNATURES = {
     "rdq_fwi_adjoint_ckpt": (c_int32, [c_void_p, c_int32, c_int32, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p,
                                        c_void_p, c_void_p, c_void_p, c_void_p]),
     "rdq_fwi_ckpt_info": (c_int32, [c_void_p, c_int32, c_int32, ctypes.POINTER(c_int32)]),
+    "rdq_fwi_forward_src": (c_int32, [c_void_p, c_int32, c_void_p, ctypes.POINTER(FwiSource), c_void_p, c_void_p,
+                                      c_void_p, c_void_p]),
+    "rdq_fwi_adjoint_src": (c_int32, [c_void_p, c_int32, c_void_p, ctypes.POINTER(FwiSource), c_void_p, c_void_p,
+                                      c_void_p, c_void_p, c_void_p, c_void_p, c_void_p]),
+    "rdq_fwi_forward_ckpt_src": (c_int32, [c_void_p, c_int32, c_int32, c_void_p, ctypes.POINTER(FwiSource), c_void_p,
+                                           c_void_p, c_void_p, c_void_p]),
+    "rdq_fwi_adjoint_ckpt_src": (c_int32, [c_void_p, c_int32, c_int32, c_void_p, ctypes.POINTER(FwiSource), c_void_p,
+                                           c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p]),
     "rdq_fwi_born_sizes": (c_int32, [c_void_p, c_int32, ctypes.POINTER(c_size_t)]),
     "rdq_fwi_dcoeffs": (c_int32, [c_void_p, c_int32, c_void_p, ctypes.POINTER(c_int64), c_int32, c_void_p, c_void_p,
                                   c_void_p, c_void_p]),

@@ -24,6 +24,10 @@ torch.compile see them as ordinary operators instead of opaque ctypes calls.
         K2 over segments recomputed into the scratch `seg` (the one mutated argument)
     red_diffeq::fwi_ckpt(v, plan, vel_mode, K) -> (seis, coeffs, vstat, ckpt)
         differentiable in v with the history bounded by recomputation (FWIForward(checkpoint=...))
+    red_diffeq::fwi_src(v, w, plan, vel_mode, keep_history) / fwi_ckpt_src(v, w, plan, vel_mode, K)
+        fwi / fwi_ckpt with the call's own wavelets w (B, ns, nt), differentiable in v and in w
+        (FWIForward.forward(v, wavelet=...)); built on fwi_forward_src / fwi_adjoint_src /
+        fwi_forward_ckpt_src / fwi_adjoint_ckpt_src (rdq_fwi_*_src), whose adjoints also return gw = d loss / d w
   U-Net (include/red_diffeq_unet.h)
     conv2d_mfma, conv2d_rms, conv2d_gn_silu, conv2d_bf16_gn_silu, conv2d_bf16_gn_silu_out, conv2d_gn_silu_sc, conv2d_gn_silu_lsm, conv2d_gn_silu_out, unet_head,
     gn_silu, rmsnorm, linear, time_mlp, linear_silu_multi, sinusoidal_emb, linear_attn, linear_attn_block, attn,
@@ -376,6 +380,223 @@ def _fwi_ckpt_backward(ctx, gseis, _gc, _gv, _gk):
 
 
 fwi_ckpt.register_autograd(_fwi_ckpt_backward, setup_context=_fwi_ckpt_setup)
+
+
+# ---- caller-supplied wavelets, per model and per shot, differentiable (rdq_fwi_*_src): always the narrow chunked
+# kernels.  `w` is (B, ns, nt) fp32 with a unit last stride; a zero stride on the first or second axis (an
+# expand() of a shared wavelet) is passed on as "shared", so nothing is materialised and autograd's own expand
+# backward sums the gradient over the shared axes.
+def _source(p, w, B, gw=None):
+    if w.dim() != 3 or tuple(w.shape) != (B, p.ns, p.nt) or w.dtype != torch.float32:
+        raise ValueError(f"fwi wavelet: expected fp32 of shape {(B, p.ns, p.nt)}, got {w.dtype} {tuple(w.shape)}")
+    if w.stride(2) != 1 or w.stride(0) < 0 or w.stride(1) < 0:
+        w = w.contiguous()
+    # (the tensor is returned too: it owns the memory the struct points to)
+    return w, _hip.FwiSource(wav=w.data_ptr(), model_stride=w.stride(0), shot_stride=w.stride(1),
+                             gwav=gw.data_ptr() if gw is not None else None)
+
+
+@torch.library.custom_op(f"{LIB}::fwi_forward_src", mutates_args=())
+def fwi_forward_src(coeffs: Tensor, w: Tensor, plan: int, B: int, keep_history: bool) -> Tuple[Tensor, Tensor]:
+    """fwi_forward with the source samples w[b, s, n] instead of the plan's wavelet."""
+    p = _plan(plan)
+    _hip.require_device(coeffs, w)
+    sz = p.sizes(B)
+    w, src = _source(p, w, B)
+    seis = torch.empty(_seis_shape(p, B), dtype=torch.float32, device=coeffs.device)
+    hist = _f32(sz.history if keep_history else 0, coeffs.device)
+    ring = _f32(sz.ring, coeffs.device)
+    _hip.check(p.lib.rdq_fwi_forward_src(p.handle, B, _hip.ptr(coeffs), ctypes.byref(src), _hip.ptr(seis),
+                                         _hip.ptr(hist) if keep_history else ctypes.c_void_p(0), _hip.ptr(ring),
+                                         _hip.stream_of(coeffs)), "rdq_fwi_forward_src")
+    return seis, hist
+
+
+@fwi_forward_src.register_fake
+def _(coeffs, w, plan, B, keep_history):
+    return _fake_forward(coeffs, plan, B, keep_history)
+
+
+def _gw_alloc(p, B, want_gw, dev):
+    return torch.empty((B, p.ns, p.nt) if want_gw else (0,), dtype=torch.float32, device=dev)
+
+
+@torch.library.custom_op(f"{LIB}::fwi_adjoint_src", mutates_args=())
+def fwi_adjoint_src(coeffs: Tensor, w: Tensor, history: Tensor, dseis: Tensor, plan: int, B: int,
+                    want_gw: bool) -> Tuple[Tensor, Tensor, Tensor, Tensor]:
+    """(gA, gk, gbeta, gw): fwi_adjoint with the source samples w, and gw = d(loss)/d(w) (B, ns, nt) where
+    want_gw (else empty: the kernel is given no gwav and nothing is allocated)."""
+    p = _plan(plan)
+    _hip.require_device(coeffs, w, history, dseis)
+    sz = p.sizes(B)
+    if dseis.shape != _seis_shape(p, B) or history.numel() * 4 != sz.history:
+        raise ValueError("fwi_adjoint_src: dseis / history do not match the plan")
+    dseis = dseis.float().contiguous()
+    gw = _gw_alloc(p, B, want_gw, coeffs.device)
+    w, src = _source(p, w, B, gw if want_gw else None)
+    ring = _f32(sz.ring, coeffs.device)
+    gA = _f32(sz.gA, coeffs.device)
+    gk = torch.empty(int(sz.gk_part) // 8, dtype=torch.float64, device=coeffs.device)
+    gb = _f32(sz.gbeta, coeffs.device)
+    _hip.check(p.lib.rdq_fwi_adjoint_src(p.handle, B, _hip.ptr(coeffs), ctypes.byref(src), _hip.ptr(history),
+                                         _hip.ptr(dseis), _hip.ptr(ring), _hip.ptr(gA), _hip.ptr(gk), _hip.ptr(gb),
+                                         _hip.stream_of(coeffs)), "rdq_fwi_adjoint_src")
+    return gA, gk, gb, gw
+
+
+def _fake_adjoint_src(coeffs, plan, B, want_gw):
+    p = _plan(plan)
+    sz = p.sizes(B)
+    return (coeffs.new_empty(int(sz.gA) // 4), coeffs.new_empty(int(sz.gk_part) // 8, dtype=torch.float64),
+            coeffs.new_empty(int(sz.gbeta) // 4), coeffs.new_empty((B, p.ns, p.nt) if want_gw else (0,)))
+
+
+@fwi_adjoint_src.register_fake
+def _(coeffs, w, history, dseis, plan, B, want_gw):
+    return _fake_adjoint_src(coeffs, plan, B, want_gw)
+
+
+@torch.library.custom_op(f"{LIB}::fwi_forward_ckpt_src", mutates_args=())
+def fwi_forward_ckpt_src(coeffs: Tensor, w: Tensor, plan: int, B: int, K: int) -> Tuple[Tensor, Tensor]:
+    """fwi_forward_ckpt with the source samples w."""
+    p = _plan(plan)
+    _hip.require_device(coeffs, w)
+    cs = p.ckpt_sizes(B, K)                      # (K < 1 raises here)
+    w, src = _source(p, w, B)
+    seis = torch.empty(_seis_shape(p, B), dtype=torch.float32, device=coeffs.device)
+    ckpt = _f32(cs.ckpt, coeffs.device)
+    ring = _f32(p.sizes(B).ring, coeffs.device)
+    _hip.check(p.lib.rdq_fwi_forward_ckpt_src(p.handle, B, K, _hip.ptr(coeffs), ctypes.byref(src), _hip.ptr(seis),
+                                              _hip.ptr(ckpt), _hip.ptr(ring), _hip.stream_of(coeffs)),
+               "rdq_fwi_forward_ckpt_src")
+    return seis, ckpt
+
+
+@fwi_forward_ckpt_src.register_fake
+def _(coeffs, w, plan, B, K):
+    p = _plan(plan)
+    return coeffs.new_empty(_seis_shape(p, B)), coeffs.new_empty(int(p.ckpt_sizes(B, K).ckpt) // 4)
+
+
+@torch.library.custom_op(f"{LIB}::fwi_adjoint_ckpt_src", mutates_args=("seg",))
+def fwi_adjoint_ckpt_src(coeffs: Tensor, w: Tensor, ckpt: Tensor, seg: Tensor, dseis: Tensor, plan: int, B: int,
+                         K: int, want_gw: bool) -> Tuple[Tensor, Tensor, Tensor, Tensor]:
+    """(gA, gk, gbeta, gw): fwi_adjoint_ckpt with the source samples w (the recompute reads them again)."""
+    p = _plan(plan)
+    _hip.require_device(coeffs, w, ckpt, seg, dseis)
+    sz, cs = p.sizes(B), p.ckpt_sizes(B, K)
+    if dseis.shape != _seis_shape(p, B):
+        raise ValueError("fwi_adjoint_ckpt_src: dseis does not match the plan")
+    if ckpt.dtype != torch.float32 or seg.dtype != torch.float32 or ckpt.numel() * 4 != cs.ckpt \
+            or seg.numel() * 4 != cs.seg or not ckpt.is_contiguous() or not seg.is_contiguous():
+        raise ValueError(f"fwi_adjoint_ckpt_src: ckpt / seg must be contiguous fp32 of {cs.ckpt} / {cs.seg} bytes "
+                         f"(K = {K}), got {ckpt.numel() * ckpt.element_size()} / {seg.numel() * seg.element_size()}")
+    dseis = dseis.float().contiguous()
+    gw = _gw_alloc(p, B, want_gw, coeffs.device)
+    w, src = _source(p, w, B, gw if want_gw else None)
+    ring = _f32(sz.ring, coeffs.device)
+    gA = _f32(sz.gA, coeffs.device)
+    gk = torch.empty(int(sz.gk_part) // 8, dtype=torch.float64, device=coeffs.device)
+    gb = _f32(sz.gbeta, coeffs.device)
+    _hip.check(p.lib.rdq_fwi_adjoint_ckpt_src(p.handle, B, K, _hip.ptr(coeffs), ctypes.byref(src), _hip.ptr(ckpt),
+                                              _hip.ptr(seg), _hip.ptr(dseis), _hip.ptr(ring), _hip.ptr(gA),
+                                              _hip.ptr(gk), _hip.ptr(gb), _hip.stream_of(coeffs)),
+               "rdq_fwi_adjoint_ckpt_src")
+    return gA, gk, gb, gw
+
+
+@fwi_adjoint_ckpt_src.register_fake
+def _(coeffs, w, ckpt, seg, dseis, plan, B, K, want_gw):
+    return _fake_adjoint_src(coeffs, plan, B, want_gw)
+
+
+@torch.library.custom_op(f"{LIB}::fwi_src", mutates_args=())
+def fwi_src(v: Tensor, w: Tensor, plan: int, vel_mode: int, keep_history: bool) -> Tuple[Tensor, Tensor, Tensor, Tensor]:
+    """seis = FWM(v; w) (K3 + K1 with the call's own wavelets); coeffs / vstat / history are for the backward."""
+    coeffs, vstat = fwi_coeffs(v, plan, vel_mode)
+    seis, hist = fwi_forward_src(coeffs, w, plan, v.shape[0], keep_history)
+    return seis, coeffs, vstat, hist
+
+
+@fwi_src.register_fake
+def _(v, w, plan, vel_mode, keep_history):
+    coeffs, vstat = _fake_coeffs(v, plan)
+    seis, hist = _fake_forward(coeffs, plan, v.shape[0], keep_history)
+    return seis, coeffs, vstat, hist
+
+
+def _fwi_src_setup(ctx, inputs, output):
+    v, w, plan, vel_mode, keep_history = inputs
+    _, coeffs, vstat, hist = output
+    ctx.mark_non_differentiable(coeffs, vstat, hist)
+    ctx.set_materialize_grads(False)
+    if not keep_history:
+        ctx.plan = None
+        return
+    ctx.plan, ctx.vel_mode, ctx.B = plan, vel_mode, v.shape[0]
+    ctx.coeffs, ctx.vstat, ctx.hist = coeffs, vstat, hist
+    ctx.save_for_backward(w)
+
+
+def _fwi_src_backward(ctx, gseis, _gc, _gv, _gh):
+    if ctx.plan is None:
+        raise RuntimeError("red_diffeq::fwi_src was called with keep_history=False; no gradient is available")
+    if gseis is None:
+        return None, None, None, None, None
+    (w,) = ctx.saved_tensors
+    want_v, want_w = ctx.needs_input_grad[0], ctx.needs_input_grad[1]
+    gA, gk, gb, gw = fwi_adjoint_src(ctx.coeffs, w, ctx.hist, gseis.contiguous(), ctx.plan, ctx.B, want_w)
+    ctx.hist = None
+    g = fwi_grad_finalize(ctx.coeffs, ctx.vstat, gA, gk, gb, ctx.plan, ctx.B, ctx.vel_mode) if want_v else None
+    return g, (gw if want_w else None), None, None, None
+
+
+fwi_src.register_autograd(_fwi_src_backward, setup_context=_fwi_src_setup)
+
+
+@torch.library.custom_op(f"{LIB}::fwi_ckpt_src", mutates_args=())
+def fwi_ckpt_src(v: Tensor, w: Tensor, plan: int, vel_mode: int, K: int) -> Tuple[Tensor, Tensor, Tensor, Tensor]:
+    """fwi_src with the history bounded by recomputation (K steps per segment), as fwi_ckpt."""
+    coeffs, vstat = fwi_coeffs(v, plan, vel_mode)
+    seis, ckpt = fwi_forward_ckpt_src(coeffs, w, plan, v.shape[0], K)
+    return seis, coeffs, vstat, ckpt
+
+
+@fwi_ckpt_src.register_fake
+def _(v, w, plan, vel_mode, K):
+    coeffs, vstat = _fake_coeffs(v, plan)
+    p = _plan(plan)
+    B = v.shape[0]
+    return (coeffs.new_empty(_seis_shape(p, B)), coeffs, vstat,
+            coeffs.new_empty(int(p.ckpt_sizes(B, K).ckpt) // 4))
+
+
+def _fwi_ckpt_src_setup(ctx, inputs, output):
+    v, w, plan, vel_mode, K = inputs
+    _, coeffs, vstat, ckpt = output
+    ctx.mark_non_differentiable(coeffs, vstat, ckpt)
+    ctx.set_materialize_grads(False)
+    ctx.plan, ctx.vel_mode, ctx.B, ctx.K = plan, vel_mode, v.shape[0], K
+    ctx.coeffs, ctx.vstat, ctx.ckpt = coeffs, vstat, ckpt
+    ctx.save_for_backward(w)
+
+
+def _fwi_ckpt_src_backward(ctx, gseis, _gc, _gv, _gk):
+    if gseis is None:
+        return None, None, None, None, None
+    p = _plan(ctx.plan)
+    (w,) = ctx.saved_tensors
+    want_v, want_w = ctx.needs_input_grad[0], ctx.needs_input_grad[1]
+    seg = _f32(p.ckpt_sizes(ctx.B, ctx.K).seg, ctx.coeffs.device)
+    gA, gk, gb, gw = fwi_adjoint_ckpt_src(ctx.coeffs, w, ctx.ckpt, seg, gseis.contiguous(), ctx.plan, ctx.B, ctx.K,
+                                          want_w)
+    ctx.ckpt = None
+    del seg
+    g = fwi_grad_finalize(ctx.coeffs, ctx.vstat, gA, gk, gb, ctx.plan, ctx.B, ctx.vel_mode) if want_v else None
+    return g, (gw if want_w else None), None, None, None
+
+
+fwi_ckpt_src.register_autograd(_fwi_ckpt_src_backward, setup_context=_fwi_ckpt_src_setup)
 
 
 # ---------------------------------------------------------------------------------------- U-Net

@@ -376,8 +376,15 @@ class FWIForward(nn.Module):
     """Drop-in for red_diffeq.solvers.pde.FWIForward (pde.py:6-93)."""
 
     def __init__(self, ctx, device, sample_temporal=1, sample_spatial=1.0, normalize=True,
-                 v_denorm_func=None, s_norm_func=None, shots=None, checkpoint=None, history_budget_gb=None):
-        """checkpoint / history_budget_gb (also read from ``ctx`` when the keyword is None, so a YAML's
+                 v_denorm_func=None, s_norm_func=None, shots=None, checkpoint=None, history_budget_gb=None,
+                 wavelet=None):
+        """wavelet: None = the Ricker wavelet of ``ctx`` (f, dt, nt), as the reference; otherwise an array-like
+        or tensor of shape (nt,), the source signature of every shot: copied to host fp64 and handed to the plan in
+        place of the Ricker (which casts it to fp32 the same way), so every kernel family, checkpointing, born /
+        gauss_newton, shots= and the engine run on it unchanged.  ricker() is then not called, so a record shorter
+        than the Ricker is legal.  Per-shot / per-model and differentiable wavelets: forward(v, wavelet=...).
+
+        checkpoint / history_budget_gb (also read from ``ctx`` when the keyword is None, so a YAML's
         ``pde:`` section can set them): None / None = the store-all history, today's path; checkpoint = K
         (int >= 1) = a checkpointed gradient with K steps per segment (two wavefield levels kept every K
         steps, each segment recomputed in the backward: 2 nt / K + K levels instead of nt + 2, one extra
@@ -413,6 +420,12 @@ class FWIForward(nn.Module):
         # shot-parallel sharding: this operator models only shots[start:stop]
         self.shots = (0, len(ctx["sx"])) if shots is None else (int(shots[0]), int(shots[1]))
         self.shots_explicit = shots is not None
+        self.wavelet = None
+        if wavelet is not None:
+            wav = wavelet.detach().cpu().numpy() if isinstance(wavelet, torch.Tensor) else np.asarray(wavelet)
+            if wav.ndim != 1 or wav.shape[0] != int(ctx["nt"]):
+                raise ValueError(f"wavelet must have shape (nt,) = ({int(ctx['nt'])},), got {tuple(wav.shape)}")
+            self.wavelet = np.array(wav, dtype=np.float64)      # the plan's own host copy
         self._plans = {}
         self._last = None
         self._fallen_back = False      # between fallback_to_chunked() and restore_persistent()
@@ -443,8 +456,13 @@ class FWIForward(nn.Module):
         return damp
 
     # --- HIP path --------------------------------------------------------------------------
-    def _plan(self, nz, nx, device):
+    def _plan(self, nz, nx, device, per_call=False):
+        """The plan of a grid shape on a device.  per_call: the caller brings its own wavelets, so a ctx whose
+        record is shorter than its Ricker wavelet, with no constructor wavelet, still gets a plan (its plan-level
+        wavelet is zeros and is marked absent: every call that would read it raises the Ricker's error)."""
         key = (nz, nx, device.index)
+        if key in self._plans and getattr(self._plans[key], "no_wavelet", False) and not per_call:
+            ricker(self.ctx["f"], self.ctx["dt"], self.ctx["nt"])      # raises: nt is shorter than the wavelet
         if key not in self._plans:
             c = self.ctx
             isx, isz, igx, igz = adj_sr(np.asarray(c["sx"]), c["sz"], np.asarray(c["gx"]), c["gz"],
@@ -452,8 +470,16 @@ class FWIForward(nn.Module):
             isx = isx[self.shots[0]:self.shots[1]]
             if len(isx) == 0:
                 raise ValueError("empty shot range")
+            wav = self.wavelet
+            if wav is None:
+                try:
+                    wav = ricker(c["f"], c["dt"], c["nt"])
+                except ValueError:
+                    if not per_call:
+                        raise
             self._plans[key] = FwiPlan(nz, nx, c, self.sample_temporal, isx, isz, igx, igz,
-                                       ricker(c["f"], c["dt"], c["nt"]), device)
+                                       wav if wav is not None else np.zeros(int(c["nt"])), device)
+            self._plans[key].no_wavelet = wav is None
             if os.environ.get("RDQ_NO_XCD_LOCAL"):       # A/B switches (tools/, experiments)
                 self._plans[key].set_variant(xcd_local=False)
             if os.environ.get("RDQ_NO_GRAPHS"):
@@ -469,7 +495,38 @@ class FWIForward(nn.Module):
     def _fused_denorm(self):
         return self.normalize and self.v_denorm_func is v_denormalize
 
-    def forward(self, v):
+    def _call_wavelet(self, v, w):
+        """Checks a per-call wavelet against v and the survey (before any device work) and returns it as this
+        operator's shots' (B, ns_local, nt) fp32 view: a shared axis is an expand(), not a copy, so autograd sums
+        its gradient, and with shots= the slice is taken in torch, so the other shots' rows get zeros."""
+        if not isinstance(w, torch.Tensor) or not w.is_floating_point():
+            raise ValueError("wavelet must be a float tensor of shape (nt,), (ns, nt) or (B, ns, nt)")
+        if v.dim() != 4 or v.shape[1] != 1:
+            raise ValueError(f"expected v of shape (B,1,H,W), got {tuple(v.shape)}")
+        B, ns, nt = v.shape[0], len(self.ctx["sx"]), int(self.ctx["nt"])
+        if w.dim() not in (1, 2, 3) or w.shape[-1] != nt or tuple(w.shape[:-1]) not in ((), (ns,), (B, ns)):
+            raise ValueError(f"wavelet must have shape ({nt},), ({ns}, {nt}) or ({B}, {ns}, {nt}) "
+                             f"(nt; shots, nt; models, shots, nt), got {tuple(w.shape)}")
+        if w.device != v.device:
+            raise ValueError(f"wavelet is on {w.device}, v on {v.device}")
+        if w.dtype != torch.float32:
+            w = w.float()
+        if w.dim() > 1:
+            w = w[..., self.shots[0]:self.shots[1], :]
+        return w.expand(B, self.shots[1] - self.shots[0], nt)
+
+    def forward(self, v, wavelet=None):
+        """seis = forward(v).  wavelet: None = the constructor's wavelet (the Ricker by default) on the plan's
+        kernels, today's path.  Otherwise a float tensor on v's device of shape (nt,), (ns, nt) or (B, ns, nt)
+        (ns = the survey's full shot count, also with shots=): sample n of model b, shot s is injected as
+        P_{n+1}[b, s, src] += beta[b, src] * w[b, s, n], and the result is differentiable in v and in the wavelet
+        (a shared wavelet receives the fp32 sum of the per-shot gradients).  Such a call always runs the narrow
+        chunked kernels (set_tuning's depths and chains), store-all or checkpointed as the instance says.  By
+        linearity J_w dw is forward(v, wavelet=dw) under no_grad.  born / gauss_newton take no wavelet: they use
+        the constructor's.  Not covered: per-call wavelets on the persistent or wide kernels, several source
+        points per shot, engine / YAML wiring of per-shot wavelets."""
+        if wavelet is not None:
+            wavelet = self._call_wavelet(v, wavelet)      # ValueError before any device work
         _hip.require_device(v)
         if v.dim() != 4 or v.shape[1] != 1:
             raise ValueError(f"expected v of shape (B,1,H,W), got {tuple(v.shape)}")
@@ -481,11 +538,16 @@ class FWIForward(nn.Module):
             if self.normalize:
                 v = self.v_denorm_func(v)     # arbitrary user callable: autograd through torch
             vel_mode = 1
-        plan = self._plan(v.shape[2], v.shape[3], v.device)
+        plan = self._plan(v.shape[2], v.shape[3], v.device, per_call=wavelet is not None)
         self._last = plan
-        keep = bool(v.requires_grad and torch.is_grad_enabled())
+        keep = bool((v.requires_grad or (wavelet is not None and wavelet.requires_grad)) and torch.is_grad_enabled())
         K = self.checkpoint_interval(plan, v.shape[0]) if keep else None
-        if K is not None:   # history bounded by recomputation; backward: recompute + K2 per segment, K4
+        if wavelet is not None:   # the call's own wavelets: narrow chunked kernels, gradients in v and w
+            if K is not None:
+                s = torch.ops.red_diffeq.fwi_ckpt_src(v, wavelet, plan.op_id, vel_mode, K)[0]
+            else:
+                s = torch.ops.red_diffeq.fwi_src(v, wavelet, plan.op_id, vel_mode, keep)[0]
+        elif K is not None:   # history bounded by recomputation; backward: recompute + K2 per segment, K4
             s = torch.ops.red_diffeq.fwi_ckpt(v, plan.op_id, vel_mode, K)[0]
         else:
             s = torch.ops.red_diffeq.fwi(v, plan.op_id, vel_mode, keep)[0]   # backward: K2 + K4 (ops.py)
@@ -551,7 +613,8 @@ class FWIForward(nn.Module):
         the byte count when history_budget_gb is set and it does not fit).  history=False: one fused time loop
         computes the forward and its tangent together and keeps no history at all (no budget applies); both
         outputs are bit-identical to history=True's.  A custom v_denorm_func, and an s_norm_func other than
-        s_normalize_none, are chained with torch.func.jvp.  With shots=, this rank's shots only, as forward."""
+        s_normalize_none, are chained with torch.func.jvp.  With shots=, this rank's shots only, as forward.  The source is
+        the constructor's wavelet (born and gauss_newton take no wavelet= of their own)."""
         v, dv, vel_mode, _ = self._linearise(v, dv, "born")
         with torch.no_grad():
             if history:
