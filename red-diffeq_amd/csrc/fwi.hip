@@ -306,8 +306,9 @@ struct FwdTBArgs {
 // exchange two boundary rows each way between the NW waves of the workgroup
 struct Halo4 { float u2, u1, d1, d2; };
 
-__device__ __forceinline__ Halo4 exchange(float (*xch)[TB_NW][4][64], int buf, int w, int lane,
-                                          float top0, float top1, float bot1, float bot0)
+template <int NW>
+__device__ __forceinline__ Halo4 exchange_nw(float (*xch)[NW][4][64], int buf, int w, int lane, float top0,
+                                             float top1, float bot1, float bot0)
 {
     xch[buf][w][0][lane] = top0;      // row 0
     xch[buf][w][1][lane] = top1;      // row 1
@@ -315,29 +316,11 @@ __device__ __forceinline__ Halo4 exchange(float (*xch)[TB_NW][4][64], int buf, i
     xch[buf][w][3][lane] = bot0;      // row R-1
     __syncthreads();
     Halo4 h;
-    const int wu = w > 0 ? w - 1 : 0, wd = w < TB_NW - 1 ? w + 1 : TB_NW - 1;
+    const int wu = w > 0 ? w - 1 : 0, wd = w < NW - 1 ? w + 1 : NW - 1;
     h.u2 = xch[buf][wu][2][lane];     // row -2 (garbage for w == 0: outside the region)
     h.u1 = xch[buf][wu][3][lane];     // row -1
     h.d1 = xch[buf][wd][0][lane];     // row R
     h.d2 = xch[buf][wd][1][lane];     // row R+1
-    return h;
-}
-
-template <int NW>
-__device__ __forceinline__ Halo4 exchange_nw(float (*xch)[NW][4][64], int buf, int w, int lane, float top0,
-                                             float top1, float bot1, float bot0)
-{
-    xch[buf][w][0][lane] = top0;
-    xch[buf][w][1][lane] = top1;
-    xch[buf][w][2][lane] = bot1;
-    xch[buf][w][3][lane] = bot0;
-    __syncthreads();
-    Halo4 h;
-    const int wu = w > 0 ? w - 1 : 0, wd = w < NW - 1 ? w + 1 : NW - 1;
-    h.u2 = xch[buf][wu][2][lane];
-    h.u1 = xch[buf][wu][3][lane];
-    h.d1 = xch[buf][wd][0][lane];
-    h.d2 = xch[buf][wd][1][lane];
     return h;
 }
 
@@ -453,13 +436,6 @@ __device__ __forceinline__ void exchange2(float (*xa)[TB_NW][4][64], float (*xb)
     hb.u2 = xb[buf][wu][2][lane]; hb.u1 = xb[buf][wu][3][lane]; hb.d1 = xb[buf][wd][0][lane]; hb.d2 = xb[buf][wd][1][lane];
 }
 
-// vertical neighbour rows of row r from the slab + halo rows
-#define TB_VERT(ARR, r, H4, m2, m1, p1, p2)                                   \
-    const float m2 = (r) >= 2 ? ARR[(r) - 2] : ((r) == 1 ? H4.u1 : H4.u2);    \
-    const float m1 = (r) >= 1 ? ARR[(r) - 1] : H4.u1;                        \
-    const float p1 = (r) + 1 < TB_R ? ARR[(r) + 1] : H4.d1;                  \
-    const float p2 = (r) + 2 < TB_R ? ARR[(r) + 2] : ((r) + 2 == TB_R ? H4.d1 : H4.d2);
-
 // XCD-aware block -> (tile, shot) map.  Blocks are dealt round-robin over the 8 XCDs (block b
 // and b+8 share an L2); every shot of one tile gets the same (block mod 8), so the per-model
 // coefficient rows a tile reads are fetched once per XCD and re-read from that L2 by the other
@@ -493,6 +469,42 @@ __device__ __forceinline__ int wrapn(int v, int n)
     return v;
 }
 
+// ---- Shared parts of the narrow chunked kernels (k_fwd_tb, k_adj_tb, k_born_tb, k_fwd_born_tb): the expressions
+// whose fp32 order the kernels' bit-exactness rests on, written once.  The kernels' header comments name the part
+// that implements each of their lines.  (The tile / row prologue, the receiver store and the ring epilogue stay in
+// the kernels: as helpers they changed the compiled text of most instantiations, DESIGN.md "Narrow chunked kernels:
+// shared parts".)
+//
+// C2 S1 + C3 S2 of row r of a field held as TB_R rows per lane, in the reference's association (pde.py:79):
+// S1 / S2 = ((up + down) + left) + right over the nearest / second neighbours.  Vertical taps: the wave's own
+// rows and the halo rows of the exchange; horizontal taps: DPP lane shifts.  Call it with every lane of the wave
+// active: a DPP read of a lane that a divergent branch has masked off returns 0 (bound_ctrl), which would corrupt
+// the tap at the tile's interior edge.  The two stars that are NOT this function, and why: k_adj_tb's gA star does
+// its arithmetic inside the branch on the interior with the shifts outside it, and k_fwd_born_tb's P star, written
+// through this function, comes out with commuted multiply operands in the GEN instantiations; both are written
+// out where they stand, in this order.
+__device__ __forceinline__ float tb_lap(const float *f, int r, const Halo4 &h)
+{
+    const float m2 = r >= 2 ? f[r - 2] : (r == 1 ? h.u1 : h.u2);
+    const float m1 = r >= 1 ? f[r - 1] : h.u1;
+    const float p1 = r + 1 < TB_R ? f[r + 1] : h.d1;
+    const float p2 = r + 2 < TB_R ? f[r + 2] : (r + 2 == TB_R ? h.d1 : h.d2);
+    const float c = f[r];
+    const float l1 = dpp_shr1(c), r1 = dpp_shl1(c);
+    const float l2 = dpp_shr1(l1), r2 = dpp_shl1(r1);
+    float s1 = m1 + p1; s1 = s1 + l1; s1 = s1 + r1;
+    float s2 = m2 + p2; s2 = s2 + l2; s2 = s2 + r2;
+    float lap = C2 * s1; const float q = C3 * s2; lap = lap + q;
+    return lap;
+}
+
+// temp1 / temp2 re-derived from alpha and kappa as gen_coef derives them (pde.py:69-70; bit-identical)
+__device__ __forceinline__ void tb_t1t2(float A, float kp, float &t1, float &t2)
+{
+    t1 = C1X2 * A; t1 = t1 + 2.0f; t1 = t1 - kp;     // pde.py:69
+    t2 = 1.0f - kp;                                  // pde.py:70
+}
+
 // SRC: the source samples are the call's own wavelets, read from a.wav (rdq_fwi_*_src) instead of the
 // kernel-argument samples a.w of the plan's wavelet; b and s are workgroup-uniform, so the launch's T
 // samples are uniform loads, hoisted ahead of the step loop.  Same operation order either way.
@@ -518,7 +530,7 @@ __global__ __launch_bounds__(64 * TB_NW) void k_fwd_tb(FwdTBArgs a)
     float A[TB_R], C1[TB_R], C2v[TB_R], P0[TB_R], P1[TB_R];
     int rofs[TB_R];                 // wave-uniform row offsets gz*ld
     unsigned rin = 0;               // wave-uniform: row is interior and inside the domain
-    int srow = -1, rrow = -1;       // wave-uniform: row holding the source / the receivers
+    int rrow = -1;                  // wave-uniform: row holding the receivers
 #pragma unroll
     for (int r = 0; r < TB_R; ++r) {
         const int uz = uz0 + r, gz = wrapn(uz, g.Hp);
@@ -534,8 +546,7 @@ __global__ __launch_bounds__(64 * TB_NW) void k_fwd_tb(FwdTBArgs a)
         P1[r] = a.in_cur[so + o];
         const int rr = w * TB_R + r;
         if (rr >= H && rr < TB_RH - H && uz < g.Hp) rin |= 1u << r;
-        if (gz == g.isz) srow = r;          // (a region row maps to one grid row: one hit per wave
-        if (gz == g.igz) rrow = r;          //  unless the region wraps a tiny domain -> see below)
+        if (gz == g.igz) rrow = r;          // (a region row maps to one grid row: one hit per wave)
     }
     // tiny domains (region taller than Hp) can hold the source row twice: keep every hit
     unsigned smask = 0;
@@ -548,7 +559,6 @@ __global__ __launch_bounds__(64 * TB_NW) void k_fwd_tb(FwdTBArgs a)
     // trip in front of every step's seismogram store
     const int rcv0 = rs < re ? g.rcv_list[rs] : -1;
     const bool rmulti = __any(re - rs > 1);               // wave-uniform: a column with several receivers
-    (void)srow;
     float ws[T];                    // SRC: w[b, s, n0 .. n0 + nsteps - 1]
     if constexpr (SRC) {
         const float *wp = a.wav + (size_t)b * a.wms + (size_t)s * a.wss + a.n0;
@@ -561,17 +571,11 @@ __global__ __launch_bounds__(64 * TB_NW) void k_fwd_tb(FwdTBArgs a)
         if (t >= a.nsteps) break;
         float *cur = (t & 1) ? P0 : P1;     // P_{n+t}
         float *prv = (t & 1) ? P1 : P0;     // P_{n+t-1}  -> overwritten with P_{n+t+1}
-        const Halo4 h4 = exchange(xch, t & 1, w, lane, cur[0], cur[1], cur[TB_R - 2], cur[TB_R - 1]);
+        const Halo4 h4 = exchange_nw<TB_NW>(xch, t & 1, w, lane, cur[0], cur[1], cur[TB_R - 2], cur[TB_R - 1]);
 #pragma unroll
         for (int r = 0; r < TB_R; ++r) {
-            TB_VERT(cur, r, h4, zm2, zm1, zp1, zp2)
             const float c = cur[r];
-            const float xl1 = dpp_shr1(c), xr1 = dpp_shl1(c);
-            const float xl2 = dpp_shr1(xl1), xr2 = dpp_shl1(xr1);
-            // pde.py:79, reference evaluation order
-            float s1 = zm1 + zp1; s1 = s1 + xl1; s1 = s1 + xr1;
-            float s2 = zm2 + zp2; s2 = s2 + xl2; s2 = s2 + xr2;
-            float lap = C2 * s1; const float l2 = C3 * s2; lap = lap + l2;
+            const float lap = tb_lap(cur, r, h4);                      // pde.py:79, reference evaluation order
             float a1 = C1[r] * c; const float a2 = C2v[r] * prv[r]; a1 = a1 - a2;
             const float a3 = A[r] * lap;
             prv[r] = a1 + a3;
@@ -644,6 +648,8 @@ struct AdjTBArgs {
 // and, on the interior only, the per-shot accumulators (loaded once, stored once per launch):
 //   gA_s += L_k (2c1 P_{k-1} + c2 S1(P_{k-1}) + c3 S2(P_{k-1})),  gk += (K P_{k-1})(L_{k+1} - L_k),
 //   gbeta[s] += L_k(src) w[k-1].
+// N1 / N2 of A L_{k+1} are tb_lap and T1 / T2 are tb_t1t2; the P star is tb_lap's expression written out, its lane
+// shifts outside the branch on the interior and its arithmetic inside.
 // SRC: w is the call's own wavelet of (b, s), loaded from a.wav (uniform loads, hoisted), and the transpose
 // of the source injection P_k(src) += beta(src) w[b, s, k-1] is
 //   gwav[b, s, k-1] = L_k(src) beta(src):   one fp32 multiply, L_k taken after step k's receiver residual,
@@ -671,7 +677,7 @@ __global__ __launch_bounds__(64 * TB_NW, 4) void k_adj_tb(AdjTBArgs a)
     const float *AL = a.coeffs + (size_t)b * g.slice;
     const float *KAp = AL + 3 * g.cstride;
     const int isx = g.isx[s];
-    float A[TB_R], L0[TB_R], L1[TB_R];   // temp1/temp2 are re-derived from A and K (bit-identical)
+    float A[TB_R], L0[TB_R], L1[TB_R];   // temp1/temp2 are re-derived from A and K (tb_t1t2)
     float gal[TB_R], kal[TB_R];          // gA_s accumulators and the sponge coefficient K, in registers
     int rofs[TB_R];
     unsigned rin = 0, pmask = 0, smask = 0, rmask = 0;   // wave-uniform row masks
@@ -751,16 +757,9 @@ __global__ __launch_bounds__(64 * TB_NW, 4) void k_adj_tb(AdjTBArgs a)
         exchange2(xch, pxc, t & 1, w, lane, qe, pe, h4, hp);
 #pragma unroll
         for (int r = 0; r < TB_R; ++r) {
-            TB_VERT(q, r, h4, qm2, qm1, qp1, qp2)
-            const float qc = q[r];
-            const float xl1 = dpp_shr1(qc), xr1 = dpp_shl1(qc);
-            const float xl2 = dpp_shr1(xl1), xr2 = dpp_shl1(xr1);
-            float n1 = qm1 + qp1; n1 = n1 + xl1; n1 = n1 + xr1;
-            float n2 = qm2 + qp2; n2 = n2 + xl2; n2 = n2 + xr2;
-            float nb = C2 * n1; const float nb2 = C3 * n2; nb = nb + nb2;
-            const float kp = kal[r];
-            float t1 = C1X2 * A[r]; t1 = t1 + 2.0f; t1 = t1 - kp;     // pde.py:69
-            const float t2 = 1.0f - kp;                               // pde.py:70
+            const float nb = tb_lap(q, r, h4);
+            float t1, t2;
+            tb_t1t2(A[r], kal[r], t1, t2);
             float l = t1 * cur[r]; const float l2 = t2 * prv[r]; l = l - l2; l = l + nb;
             prv[r] = l;
         }
@@ -772,7 +771,9 @@ __global__ __launch_bounds__(64 * TB_NW, 4) void k_adj_tb(AdjTBArgs a)
         // gradient accumulators on the interior (P halo rows came with the same exchange)
 #pragma unroll
         for (int r = 0; r < TB_R; ++r) {
-            TB_VERT(P, r, hp, pm2, pm1, pp1, pp2)
+            // tb_lap's star of P, written out: the DPP shifts here, with every lane active, the arithmetic inside the branch
+            const float pm2 = r >= 2 ? P[r - 2] : (r == 1 ? hp.u1 : hp.u2), pm1 = r >= 1 ? P[r - 1] : hp.u1;
+            const float pp1 = r + 1 < TB_R ? P[r + 1] : hp.d1, pp2 = r + 2 < TB_R ? P[r + 2] : (r + 2 == TB_R ? hp.d1 : hp.d2);
             const float pc = P[r];
             const float xl1 = dpp_shr1(pc), xr1 = dpp_shl1(pc);
             const float xl2 = dpp_shr1(xl1), xr2 = dpp_shl1(xr1);
@@ -945,9 +946,9 @@ struct BornTBArgs {
 //
 // Operation order (contraction off), per cell and step; S1 / S2 = the four nearest / second neighbours summed as
 // ((up + down) + left) + right:
-//   lap  = C2 S1(dP_n) + C3 S2(dP_n)
-//   hom  = (T1 dP_n - T2 dP_{n-1}) + A lap                              the forward's own order
-//   d    = 2c1 P_n + (C2 S1(P_n) + C3 S2(P_n))                          k_adj_tb's gA factor
+//   lap  = C2 S1(dP_n) + C3 S2(dP_n)                                    tb_lap
+//   hom  = (T1 dP_n - T2 dP_{n-1}) + A lap                              the forward's own order; T1, T2: tb_t1t2
+//   d    = 2c1 P_n + (C2 S1(P_n) + C3 S2(P_n))                          k_adj_tb's gA factor (tb_lap)
 //   f    = dA d - (K ratio)(P_n - P_{n-1})
 //   dP_{n+1} = hom + f, then + dbeta w[n] at the source cell
 // with dA from the prologue; a recorded value is stored as dP 2^k (the scale above).
@@ -1032,25 +1033,14 @@ __global__ __launch_bounds__(64 * TB_NW) void k_born_tb(BornTBArgs a)
         exchange2(xch, pxc, t & 1, w, lane, de, pe, hd, hp);
 #pragma unroll
         for (int r = 0; r < TB_R; ++r) {
-            TB_VERT(cur, r, hd, zm2, zm1, zp1, zp2)
-            const float c = cur[r];
-            const float xl1 = dpp_shr1(c), xr1 = dpp_shl1(c);
-            const float xl2 = dpp_shr1(xl1), xr2 = dpp_shl1(xr1);
-            float s1 = zm1 + zp1; s1 = s1 + xl1; s1 = s1 + xr1;
-            float s2 = zm2 + zp2; s2 = s2 + xl2; s2 = s2 + xr2;
-            float lap = C2 * s1; const float l2 = C3 * s2; lap = lap + l2;
-            const float kp = K[r];
-            float t1 = C1X2 * A[r]; t1 = t1 + 2.0f; t1 = t1 - kp;     // pde.py:69
-            const float t2 = 1.0f - kp;                               // pde.py:70
+            const float c = cur[r], kp = K[r];
+            const float lap = tb_lap(cur, r, hd);
+            float t1, t2;
+            tb_t1t2(A[r], kp, t1, t2);
             float hom = t1 * c; const float a2 = t2 * prv[r]; hom = hom - a2;
             const float a3 = A[r] * lap; hom = hom + a3;
-            TB_VERT(P, r, hp, pm2, pm1, pp1, pp2)
             const float pc = P[r];
-            const float pl1 = dpp_shr1(pc), pr1 = dpp_shl1(pc);
-            const float pl2 = dpp_shr1(pl1), pr2 = dpp_shl1(pr1);
-            float q1 = pm1 + pp1; q1 = q1 + pl1; q1 = q1 + pr1;
-            float q2 = pm2 + pp2; q2 = q2 + pl2; q2 = q2 + pr2;
-            float plap = C2 * q1; const float pq = C3 * q2; plap = plap + pq;
+            const float plap = tb_lap(P, r, hp);
             float d = C1X2 * pc; d = d + plap;
             float f = dA[r] * d;
             const float dk = kp * ratio, dp = pc - Pp[r];
@@ -1108,10 +1098,10 @@ struct FwdBornTBArgs {
 //
 // Operation order (contraction off).  d's stencil term and the forward's lap are the same expression of P_n in
 // the same association, so it is evaluated once:
-//   plap = C2 S1(P_n) + C3 S2(P_n)
+//   plap = C2 S1(P_n) + C3 S2(P_n)                                      tb_lap's expression, written out
 //   dP_{n+1} as in k_born_tb (lap, hom, d = 2c1 P_n + plap, f, then + dbeta w[n] at the source cell)
 //   P_{n+1}  = (T1 P_n - T2 P_{n-1}) + A plap, then + beta w[n] at the source cell    (k_fwd_tb's order)
-// with T1 / T2 re-derived from A and K as gen_coef derives them (k_adj_tb, k_born_tb).  The forward's bits are
+// with T1 / T2 re-derived from A and K as gen_coef derives them (tb_t1t2, as k_adj_tb and k_born_tb).  The forward's bits are
 // therefore the stored history's bits: dseis is bit-identical to rdq_fwi_born's and seis to rdq_fwi_forward's.
 template <int T, bool GEN>
 __global__ __launch_bounds__(64 * TB_NW) void k_fwd_born_tb(FwdBornTBArgs a)
@@ -1180,19 +1170,15 @@ __global__ __launch_bounds__(64 * TB_NW) void k_fwd_born_tb(FwdBornTBArgs a)
         exchange2(xch, pxc, t & 1, w, lane, de, pe, hd, hp);
 #pragma unroll
         for (int r = 0; r < TB_R; ++r) {
-            TB_VERT(cur, r, hd, zm2, zm1, zp1, zp2)
-            const float c = cur[r];
-            const float xl1 = dpp_shr1(c), xr1 = dpp_shl1(c);
-            const float xl2 = dpp_shr1(xl1), xr2 = dpp_shl1(xr1);
-            float s1 = zm1 + zp1; s1 = s1 + xl1; s1 = s1 + xr1;
-            float s2 = zm2 + zp2; s2 = s2 + xl2; s2 = s2 + xr2;
-            float lap = C2 * s1; const float l2 = C3 * s2; lap = lap + l2;
-            const float kp = K[r];
-            float t1 = C1X2 * A[r]; t1 = t1 + 2.0f; t1 = t1 - kp;     // pde.py:69
-            const float t2 = 1.0f - kp;                               // pde.py:70
+            const float c = cur[r], kp = K[r];
+            const float lap = tb_lap(cur, r, hd);
+            float t1, t2;
+            tb_t1t2(A[r], kp, t1, t2);
             float hom = t1 * c; const float a2 = t2 * prv[r]; hom = hom - a2;
             const float a3 = A[r] * lap; hom = hom + a3;
-            TB_VERT(P, r, hp, pm2, pm1, pp1, pp2)
+            // tb_lap's star of P, written out (see tb_lap)
+            const float pm2 = r >= 2 ? P[r - 2] : (r == 1 ? hp.u1 : hp.u2), pm1 = r >= 1 ? P[r - 1] : hp.u1;
+            const float pp1 = r + 1 < TB_R ? P[r + 1] : hp.d1, pp2 = r + 2 < TB_R ? P[r + 2] : (r + 2 == TB_R ? hp.d1 : hp.d2);
             const float pc = P[r], pv = Pp[r];
             const float pl1 = dpp_shr1(pc), pr1 = dpp_shl1(pc);
             const float pl2 = dpp_shr1(pl1), pr2 = dpp_shl1(pr1);
@@ -3082,7 +3068,6 @@ __global__ __launch_bounds__(64 * NW) void k_adj_pr(AdjPtArgs a)
 #undef PT_REGION_HEAD
 #undef PT_REGION_GEOM
 #undef LAUNDER
-#undef TB_VERT
 
 // Receivers sharing a padded column (ng > nx, or repeated gx): their residuals at one (model, shot,
 // record) summed in receiver order into one value per column, the gradient the reference's
@@ -4288,6 +4273,16 @@ struct ChunkBufs {
     const rdq_fwi_source *src;       // the call's own wavelets (rdq_fwi_*_src), or nullptr: the plan's
 };
 
+// What every time-loop launch sets the same way in its kernel arguments: the launch's shots and tile grid, and the
+// wavelet samples of its steps (forward kinds: w[first + t]; adjoint: w[first - 1 - t]; zero past nsteps).
+template <int N>
+void launch_geo_and_wavelet(TBGeo &g, float (&w)[N], const Launch &l, const std::vector<float> &wavf)
+{
+    g.s_off = l.s_off; g.ns_grp = l.ns_grp; g.tiles_x = l.tiles_x; g.ntiles = l.ntiles;
+    const bool adj = l.kind == Launch::adj;
+    for (int t = 0; t < N; ++t) w[t] = t < l.nsteps ? wavf[adj ? l.first - 1 - t : l.first + t] : 0.0f;
+}
+
 int enqueue_chunked(rdq_fwi_plan *p, int B, Pass pass, int K, const ChunkBufs &b, hipStream_t st)
 {
     const bool src = b.src != nullptr;
@@ -4345,34 +4340,30 @@ int enqueue_chunked(rdq_fwi_plan *p, int B, Pass pass, int K, const ChunkBufs &b
             hipLaunchKernelGGL(k_ckpt_levels, dim3(gx, 2 * B), dim3(256), 0, cs, level(l.in, 0), level(l.out, 0), L,
                                (size_t)ns * slice, (size_t)l.s_off * slice, run, B);
         } else if (l.kind == Launch::fwd) {
-            f.g.s_off = l.s_off; f.g.ns_grp = l.ns_grp; f.g.tiles_x = l.tiles_x; f.g.ntiles = l.ntiles;
+            launch_geo_and_wavelet(f.g, f.w, l, p->wavf);
             f.ns_sh = l.ns_sh; f.spw = l.spw;
             f.n0 = l.first; f.nsteps = l.nsteps; f.hbase = l.hbase;
-            for (int t = 0; t < FWD_W_MAX; ++t) f.w[t] = t < l.nsteps ? p->wavf[l.first + t] : 0.0f;
             f.in_prev = level(l.in, 0); f.in_cur = level(l.in, 1);
             f.out_prev = level(l.out, 0); f.out_cur = level(l.out, 1);
             launch_kernel(src ? fwd_tb_src_kernel(p->fwd_T, p->fwd_gen) : chunk_fwd_kernel(p, l.nsteps), l.grid, cs, f);
         } else if (l.kind == Launch::born) {
-            d.g.s_off = l.s_off; d.g.ns_grp = l.ns_grp; d.g.tiles_x = l.tiles_x; d.g.ntiles = l.ntiles;
+            launch_geo_and_wavelet(d.g, d.w, l, p->wavf);
             d.n0 = l.first; d.nsteps = l.nsteps;
-            for (int t = 0; t < TB_MAXT; ++t) d.w[t] = t < l.nsteps ? p->wavf[l.first + t] : 0.0f;
             d.in_prev = level(l.in, 0); d.in_cur = level(l.in, 1);
             d.out_prev = level(l.out, 0); d.out_cur = level(l.out, 1);
             launch_kernel(born_tb_kernel(p->fwd_T, p->fwd_gen), l.grid, cs, d);
         } else if (l.kind == Launch::fwd_born) {
-            u.g.s_off = l.s_off; u.g.ns_grp = l.ns_grp; u.g.tiles_x = l.tiles_x; u.g.ntiles = l.ntiles;
+            launch_geo_and_wavelet(u.g, u.w, l, p->wavf);
             u.n0 = l.first; u.nsteps = l.nsteps;
-            for (int t = 0; t < TB_MAXT; ++t) u.w[t] = t < l.nsteps ? p->wavf[l.first + t] : 0.0f;
             u.p_in_prev = level(l.in, 0); u.p_in_cur = level(l.in, 1);
             u.p_out_prev = level(l.out, 0); u.p_out_cur = level(l.out, 1);
             u.in_prev = level(l.in2, 0); u.in_cur = level(l.in2, 1);
             u.out_prev = level(l.out2, 0); u.out_cur = level(l.out2, 1);
             launch_kernel(fwd_born_tb_kernel(p->fwd_T, p->fwd_gen), l.grid, cs, u);
         } else {
-            a.g.s_off = l.s_off; a.g.ns_grp = l.ns_grp; a.g.tiles_x = l.tiles_x; a.g.ntiles = l.ntiles;
+            launch_geo_and_wavelet(a.g, a.w, l, p->wavf);
             a.ns_sh = l.ns_sh; a.spw = l.spw;
             a.k0 = l.first; a.nsteps = l.nsteps; a.hbase = l.hbase;
-            for (int t = 0; t < ADJ_W_MAX; ++t) a.w[t] = t < l.nsteps ? p->wavf[l.first - 1 - t] : 0.0f;
             a.in_l1 = level(l.in, 0); a.in_l2 = level(l.in, 1);
             a.out_l1 = level(l.out, 0); a.out_l2 = level(l.out, 1);
             launch_kernel(src ? adj_tb_src_kernel(p->adj_T) : chunk_adj_kernel(p, l.nsteps), l.grid, cs, a);

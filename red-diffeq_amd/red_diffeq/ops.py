@@ -101,51 +101,116 @@ def _seis_shape(p, B):
     return (B, p.ns, p.sizes(B).nrec, p.ng)
 
 
-@torch.library.custom_op(f"{LIB}::fwi_forward", mutates_args=())
-def fwi_forward(coeffs: Tensor, plan: int, B: int, keep_history: bool) -> Tuple[Tensor, Tensor]:
+def _fake_coeffs(v, plan):
+    sz = _plan(plan).sizes(v.shape[0])
+    return v.new_empty(int(sz.coeffs) // 4, dtype=torch.float32), v.new_empty(int(sz.vstat), dtype=torch.uint8)
+
+
+def _fake_forward(coeffs, plan, B, keep_history=False, K=None):
+    """(seis, store): store = the history (K None; empty unless keep_history) or the checkpoint store for K."""
     p = _plan(plan)
-    _hip.require_device(coeffs)
+    nbytes = p.ckpt_sizes(B, K).ckpt if K is not None else (p.sizes(B).history if keep_history else 0)
+    return coeffs.new_empty(_seis_shape(p, B)), coeffs.new_empty(int(nbytes) // 4)
+
+
+def _fake_adjoint(coeffs, plan, B, want_gw=None):
+    """The accumulators (gA, gk, gbeta), and with want_gw given (the _src ops) also gw."""
+    p = _plan(plan)
     sz = p.sizes(B)
+    acc = (coeffs.new_empty(int(sz.gA) // 4), coeffs.new_empty(int(sz.gk_part) // 8, dtype=torch.float64),
+           coeffs.new_empty(int(sz.gbeta) // 4))
+    return acc if want_gw is None else acc + (coeffs.new_empty((B, p.ns, p.nt) if want_gw else (0,)),)
+
+
+# Caller-supplied wavelets, per model and per shot, differentiable (rdq_fwi_*_src): always the narrow chunked
+# kernels.  `w` is (B, ns, nt) fp32 with a unit last stride; a zero stride on the first or second axis (an
+# expand() of a shared wavelet) is passed on as "shared", so nothing is materialised and autograd's own expand
+# backward sums the gradient over the shared axes.
+def _source(p, w, B, gw=None):
+    if w.dim() != 3 or tuple(w.shape) != (B, p.ns, p.nt) or w.dtype != torch.float32:
+        raise ValueError(f"fwi wavelet: expected fp32 of shape {(B, p.ns, p.nt)}, got {w.dtype} {tuple(w.shape)}")
+    if w.stride(2) != 1 or w.stride(0) < 0 or w.stride(1) < 0:
+        w = w.contiguous()
+    # (the tensor is returned too: it owns the memory the struct points to)
+    return w, _hip.FwiSource(wav=w.data_ptr(), model_stride=w.stride(0), shot_stride=w.stride(1),
+                             gwav=gw.data_ptr() if gw is not None else None)
+
+
+def _run_forward(coeffs, plan, B, keep_history=False, K=None, w=None):
+    """The one forward behind fwi_forward{,_ckpt}{,_src}: rdq_fwi_forward{,_ckpt}{,_src}.  K: checkpoints every K
+    steps instead of a history; w: the call's own wavelets.  Returns (seis, history | ckpt)."""
+    p = _plan(plan)
+    _hip.require_device(coeffs, w)
+    sz = p.sizes(B)
+    nstore = p.ckpt_sizes(B, K).ckpt if K is not None else (sz.history if keep_history else 0)   # (K < 1 raises here)
+    entry = "rdq_fwi_forward" + ("_ckpt" if K is not None else "") + ("_src" if w is not None else "")
+    if w is not None:
+        w, src = _source(p, w, B)
     seis = torch.empty(_seis_shape(p, B), dtype=torch.float32, device=coeffs.device)
-    hist = _f32(sz.history if keep_history else 0, coeffs.device)
+    store = _f32(nstore, coeffs.device)
     ring = _f32(sz.ring, coeffs.device)
-    _hip.check(p.lib.rdq_fwi_forward(p.handle, B, _hip.ptr(coeffs), _hip.ptr(seis),
-                                     _hip.ptr(hist) if keep_history else ctypes.c_void_p(0), _hip.ptr(ring),
-                                     _hip.stream_of(coeffs)), "rdq_fwi_forward")
-    return seis, hist
+    args = [p.handle, B] + ([K] if K is not None else []) + [_hip.ptr(coeffs)]
+    args += [ctypes.byref(src)] if w is not None else []
+    args += [_hip.ptr(seis), _hip.ptr(store) if K is not None or keep_history else ctypes.c_void_p(0), _hip.ptr(ring),
+             _hip.stream_of(coeffs)]
+    _hip.check(getattr(p.lib, entry)(*args), entry)
+    return seis, store
 
 
-@fwi_forward.register_fake
-def _(coeffs, plan, B, keep_history):
+def _run_adjoint(op, coeffs, dseis, plan, B, history=None, ckpt=None, seg=None, K=None, w=None, want_gw=False):
+    """The one adjoint behind fwi_adjoint{,_ckpt}{,_src}: rdq_fwi_adjoint{,_ckpt}{,_src} over a stored `history`, or
+    (K) over the checkpoint store `ckpt` with every segment recomputed into the scratch `seg`.  `op` names the public
+    op in error messages.  Returns (gA, gk, gbeta, gw); gw is empty unless want_gw."""
     p = _plan(plan)
+    _hip.require_device(coeffs, w, history, ckpt, seg, dseis)
     sz = p.sizes(B)
-    return (coeffs.new_empty(_seis_shape(p, B)),
-            coeffs.new_empty(int(sz.history) // 4 if keep_history else 0))
-
-
-@torch.library.custom_op(f"{LIB}::fwi_adjoint", mutates_args=())
-def fwi_adjoint(coeffs: Tensor, history: Tensor, dseis: Tensor, plan: int, B: int) -> Tuple[Tensor, Tensor, Tensor]:
-    p = _plan(plan)
-    _hip.require_device(coeffs, history, dseis)
-    sz = p.sizes(B)
-    if dseis.shape != _seis_shape(p, B) or history.numel() * 4 != sz.history:
-        raise ValueError("fwi_adjoint: dseis / history do not match the plan")
+    if K is None:
+        if dseis.shape != _seis_shape(p, B) or history.numel() * 4 != sz.history:
+            raise ValueError(f"{op}: dseis / history do not match the plan")
+        stores = [_hip.ptr(history)]
+    else:
+        cs = p.ckpt_sizes(B, K)
+        if dseis.shape != _seis_shape(p, B):
+            raise ValueError(f"{op}: dseis does not match the plan")
+        if ckpt.dtype != torch.float32 or seg.dtype != torch.float32 or ckpt.numel() * 4 != cs.ckpt \
+                or seg.numel() * 4 != cs.seg or not ckpt.is_contiguous() or not seg.is_contiguous():
+            raise ValueError(f"{op}: ckpt / seg must be contiguous fp32 of {cs.ckpt} / {cs.seg} bytes "
+                             f"(K = {K}), got {ckpt.numel() * ckpt.element_size()} / {seg.numel() * seg.element_size()}")
+        stores = [_hip.ptr(ckpt), _hip.ptr(seg)]
     dseis = dseis.float().contiguous()
+    gw = torch.empty((B, p.ns, p.nt) if want_gw else (0,), dtype=torch.float32, device=coeffs.device)
+    entry = "rdq_fwi_adjoint" + ("_ckpt" if K is not None else "") + ("_src" if w is not None else "")
+    if w is not None:
+        w, src = _source(p, w, B, gw if want_gw else None)
     ring = _f32(sz.ring, coeffs.device)
     gA = _f32(sz.gA, coeffs.device)
     gk = torch.empty(int(sz.gk_part) // 8, dtype=torch.float64, device=coeffs.device)
     gb = _f32(sz.gbeta, coeffs.device)
-    _hip.check(p.lib.rdq_fwi_adjoint(p.handle, B, _hip.ptr(coeffs), _hip.ptr(history), _hip.ptr(dseis),
-                                     _hip.ptr(ring), _hip.ptr(gA), _hip.ptr(gk), _hip.ptr(gb),
-                                     _hip.stream_of(coeffs)), "rdq_fwi_adjoint")
-    return gA, gk, gb
+    args = [p.handle, B] + ([K] if K is not None else []) + [_hip.ptr(coeffs)]
+    args += [ctypes.byref(src)] if w is not None else []
+    args += stores + [_hip.ptr(dseis), _hip.ptr(ring), _hip.ptr(gA), _hip.ptr(gk), _hip.ptr(gb), _hip.stream_of(coeffs)]
+    _hip.check(getattr(p.lib, entry)(*args), entry)
+    return gA, gk, gb, gw
+
+
+@torch.library.custom_op(f"{LIB}::fwi_forward", mutates_args=())
+def fwi_forward(coeffs: Tensor, plan: int, B: int, keep_history: bool) -> Tuple[Tensor, Tensor]:
+    return _run_forward(coeffs, plan, B, keep_history)
+
+
+@fwi_forward.register_fake
+def _(coeffs, plan, B, keep_history):
+    return _fake_forward(coeffs, plan, B, keep_history)
+
+
+@torch.library.custom_op(f"{LIB}::fwi_adjoint", mutates_args=())
+def fwi_adjoint(coeffs: Tensor, history: Tensor, dseis: Tensor, plan: int, B: int) -> Tuple[Tensor, Tensor, Tensor]:
+    return _run_adjoint("fwi_adjoint", coeffs, dseis, plan, B, history=history)[:3]
 
 
 @fwi_adjoint.register_fake
 def _(coeffs, history, dseis, plan, B):
-    sz = _plan(plan).sizes(B)
-    return (coeffs.new_empty(int(sz.gA) // 4), coeffs.new_empty(int(sz.gk_part) // 8, dtype=torch.float64),
-            coeffs.new_empty(int(sz.gbeta) // 4))
+    return _fake_adjoint(coeffs, plan, B)
 
 
 @torch.library.custom_op(f"{LIB}::fwi_grad_finalize", mutates_args=())
@@ -166,58 +231,6 @@ def fwi_grad_finalize(coeffs: Tensor, vstat: Tensor, gA: Tensor, gk: Tensor, gbe
 def _(coeffs, vstat, gA, gk, gbeta, plan, B, vel_mode):
     p = _plan(plan)
     return coeffs.new_empty(B, 1, p.nz, p.nx)
-
-
-@torch.library.custom_op(f"{LIB}::fwi", mutates_args=())
-def fwi(v: Tensor, plan: int, vel_mode: int, keep_history: bool) -> Tuple[Tensor, Tensor, Tensor, Tensor]:
-    """seis = FWM(v) (K3 + K1); coeffs / vstat / history are returned for the backward."""
-    coeffs, vstat = fwi_coeffs(v, plan, vel_mode)
-    seis, hist = fwi_forward(coeffs, plan, v.shape[0], keep_history)
-    return seis, coeffs, vstat, hist
-
-
-@fwi.register_fake
-def _(v, plan, vel_mode, keep_history):
-    coeffs, vstat = _fake_coeffs(v, plan)
-    seis, hist = _fake_forward(coeffs, plan, v.shape[0], keep_history)
-    return seis, coeffs, vstat, hist
-
-
-def _fake_coeffs(v, plan):
-    sz = _plan(plan).sizes(v.shape[0])
-    return v.new_empty(int(sz.coeffs) // 4, dtype=torch.float32), v.new_empty(int(sz.vstat), dtype=torch.uint8)
-
-
-def _fake_forward(coeffs, plan, B, keep_history):
-    p = _plan(plan)
-    sz = p.sizes(B)
-    return coeffs.new_empty(_seis_shape(p, B)), coeffs.new_empty(int(sz.history) // 4 if keep_history else 0)
-
-
-def _fwi_setup(ctx, inputs, output):
-    v, plan, vel_mode, keep_history = inputs
-    _, coeffs, vstat, hist = output
-    # only seis is differentiable: no zero "gradients" are materialised for the saved buffers
-    # (a zeros_like of the history would be a multi-GB fill per backward)
-    ctx.mark_non_differentiable(coeffs, vstat, hist)
-    ctx.set_materialize_grads(False)
-    if not keep_history:
-        ctx.plan = None
-        return
-    ctx.plan, ctx.vel_mode, ctx.B = plan, vel_mode, v.shape[0]
-    ctx.coeffs, ctx.vstat, ctx.hist = coeffs, vstat, hist
-
-
-def _fwi_backward(ctx, gseis, _gc, _gv, _gh):
-    if ctx.plan is None:
-        raise RuntimeError("red_diffeq::fwi was called with keep_history=False; no gradient is available")
-    gA, gk, gb = fwi_adjoint(ctx.coeffs, ctx.hist, gseis.contiguous(), ctx.plan, ctx.B)
-    ctx.hist = None                     # the largest buffer: released as soon as the adjoint has run
-    g = fwi_grad_finalize(ctx.coeffs, ctx.vstat, gA, gk, gb, ctx.plan, ctx.B, ctx.vel_mode)
-    return g, None, None, None
-
-
-fwi.register_autograd(_fwi_backward, setup_context=_fwi_setup)
 
 
 # ---- linearised (Born) forward: J dv over the stored history (rdq_fwi_dcoeffs + rdq_fwi_born)
@@ -295,52 +308,94 @@ def _(coeffs, vstat, dv, plan, B, vel_mode, K):
 @torch.library.custom_op(f"{LIB}::fwi_forward_ckpt", mutates_args=())
 def fwi_forward_ckpt(coeffs: Tensor, plan: int, B: int, K: int) -> Tuple[Tensor, Tensor]:
     """First pass: (seis, ckpt), ckpt = two wavefield levels per interior segment boundary."""
-    p = _plan(plan)
-    _hip.require_device(coeffs)
-    cs = p.ckpt_sizes(B, K)                      # (K < 1 raises here)
-    seis = torch.empty(_seis_shape(p, B), dtype=torch.float32, device=coeffs.device)
-    ckpt = _f32(cs.ckpt, coeffs.device)
-    ring = _f32(p.sizes(B).ring, coeffs.device)
-    _hip.check(p.lib.rdq_fwi_forward_ckpt(p.handle, B, K, _hip.ptr(coeffs), _hip.ptr(seis), _hip.ptr(ckpt),
-                                          _hip.ptr(ring), _hip.stream_of(coeffs)), "rdq_fwi_forward_ckpt")
-    return seis, ckpt
+    return _run_forward(coeffs, plan, B, K=K)
 
 
 @fwi_forward_ckpt.register_fake
 def _(coeffs, plan, B, K):
-    p = _plan(plan)
-    return coeffs.new_empty(_seis_shape(p, B)), coeffs.new_empty(int(p.ckpt_sizes(B, K).ckpt) // 4)
+    return _fake_forward(coeffs, plan, B, K=K)
 
 
 @torch.library.custom_op(f"{LIB}::fwi_adjoint_ckpt", mutates_args=("seg",))
 def fwi_adjoint_ckpt(coeffs: Tensor, ckpt: Tensor, seg: Tensor, dseis: Tensor, plan: int, B: int,
                      K: int) -> Tuple[Tensor, Tensor, Tensor]:
     """Backward: every segment recomputed into the scratch `seg`, then its adjoint; (gA, gk, gbeta)."""
-    p = _plan(plan)
-    _hip.require_device(coeffs, ckpt, seg, dseis)
-    sz, cs = p.sizes(B), p.ckpt_sizes(B, K)
-    if dseis.shape != _seis_shape(p, B):
-        raise ValueError("fwi_adjoint_ckpt: dseis does not match the plan")
-    if ckpt.dtype != torch.float32 or seg.dtype != torch.float32 or ckpt.numel() * 4 != cs.ckpt \
-            or seg.numel() * 4 != cs.seg or not ckpt.is_contiguous() or not seg.is_contiguous():
-        raise ValueError(f"fwi_adjoint_ckpt: ckpt / seg must be contiguous fp32 of {cs.ckpt} / {cs.seg} bytes "
-                         f"(K = {K}), got {ckpt.numel() * ckpt.element_size()} / {seg.numel() * seg.element_size()}")
-    dseis = dseis.float().contiguous()
-    ring = _f32(sz.ring, coeffs.device)
-    gA = _f32(sz.gA, coeffs.device)
-    gk = torch.empty(int(sz.gk_part) // 8, dtype=torch.float64, device=coeffs.device)
-    gb = _f32(sz.gbeta, coeffs.device)
-    _hip.check(p.lib.rdq_fwi_adjoint_ckpt(p.handle, B, K, _hip.ptr(coeffs), _hip.ptr(ckpt), _hip.ptr(seg),
-                                          _hip.ptr(dseis), _hip.ptr(ring), _hip.ptr(gA), _hip.ptr(gk), _hip.ptr(gb),
-                                          _hip.stream_of(coeffs)), "rdq_fwi_adjoint_ckpt")
-    return gA, gk, gb
+    return _run_adjoint("fwi_adjoint_ckpt", coeffs, dseis, plan, B, ckpt=ckpt, seg=seg, K=K)[:3]
 
 
 @fwi_adjoint_ckpt.register_fake
 def _(coeffs, ckpt, seg, dseis, plan, B, K):
-    sz = _plan(plan).sizes(B)
-    return (coeffs.new_empty(int(sz.gA) // 4), coeffs.new_empty(int(sz.gk_part) // 8, dtype=torch.float64),
-            coeffs.new_empty(int(sz.gbeta) // 4))
+    return _fake_adjoint(coeffs, plan, B)
+
+
+# ---- the call's own wavelets (rdq_fwi_*_src; _source above)
+@torch.library.custom_op(f"{LIB}::fwi_forward_src", mutates_args=())
+def fwi_forward_src(coeffs: Tensor, w: Tensor, plan: int, B: int, keep_history: bool) -> Tuple[Tensor, Tensor]:
+    """fwi_forward with the source samples w[b, s, n] instead of the plan's wavelet."""
+    return _run_forward(coeffs, plan, B, keep_history, w=w)
+
+
+@fwi_forward_src.register_fake
+def _(coeffs, w, plan, B, keep_history):
+    return _fake_forward(coeffs, plan, B, keep_history)
+
+
+@torch.library.custom_op(f"{LIB}::fwi_adjoint_src", mutates_args=())
+def fwi_adjoint_src(coeffs: Tensor, w: Tensor, history: Tensor, dseis: Tensor, plan: int, B: int,
+                    want_gw: bool) -> Tuple[Tensor, Tensor, Tensor, Tensor]:
+    """(gA, gk, gbeta, gw): fwi_adjoint with the source samples w, and gw = d(loss)/d(w) (B, ns, nt) where
+    want_gw (else empty: the kernel is given no gwav and nothing is allocated)."""
+    return _run_adjoint("fwi_adjoint_src", coeffs, dseis, plan, B, history=history, w=w, want_gw=want_gw)
+
+
+@fwi_adjoint_src.register_fake
+def _(coeffs, w, history, dseis, plan, B, want_gw):
+    return _fake_adjoint(coeffs, plan, B, want_gw)
+
+
+@torch.library.custom_op(f"{LIB}::fwi_forward_ckpt_src", mutates_args=())
+def fwi_forward_ckpt_src(coeffs: Tensor, w: Tensor, plan: int, B: int, K: int) -> Tuple[Tensor, Tensor]:
+    """fwi_forward_ckpt with the source samples w."""
+    return _run_forward(coeffs, plan, B, K=K, w=w)
+
+
+@fwi_forward_ckpt_src.register_fake
+def _(coeffs, w, plan, B, K):
+    return _fake_forward(coeffs, plan, B, K=K)
+
+
+@torch.library.custom_op(f"{LIB}::fwi_adjoint_ckpt_src", mutates_args=("seg",))
+def fwi_adjoint_ckpt_src(coeffs: Tensor, w: Tensor, ckpt: Tensor, seg: Tensor, dseis: Tensor, plan: int, B: int,
+                         K: int, want_gw: bool) -> Tuple[Tensor, Tensor, Tensor, Tensor]:
+    """(gA, gk, gbeta, gw): fwi_adjoint_ckpt with the source samples w (the recompute reads them again)."""
+    return _run_adjoint("fwi_adjoint_ckpt_src", coeffs, dseis, plan, B, ckpt=ckpt, seg=seg, K=K, w=w, want_gw=want_gw)
+
+
+@fwi_adjoint_ckpt_src.register_fake
+def _(coeffs, w, ckpt, seg, dseis, plan, B, K, want_gw):
+    return _fake_adjoint(coeffs, plan, B, want_gw)
+
+
+# ---- the differentiable operators FWIForward calls: K3 + a forward, with the adjoint + K4 as the backward.
+# Outputs (seis, coeffs, vstat, store): only seis is differentiable; coeffs / vstat / the history or checkpoint
+# store are returned for the backward.
+def _fake_fwi(v, plan, keep_history=False, K=None):
+    coeffs, vstat = _fake_coeffs(v, plan)
+    seis, store = _fake_forward(coeffs, plan, v.shape[0], keep_history, K)
+    return seis, coeffs, vstat, store
+
+
+@torch.library.custom_op(f"{LIB}::fwi", mutates_args=())
+def fwi(v: Tensor, plan: int, vel_mode: int, keep_history: bool) -> Tuple[Tensor, Tensor, Tensor, Tensor]:
+    """seis = FWM(v) (K3 + K1); coeffs / vstat / history are returned for the backward."""
+    coeffs, vstat = fwi_coeffs(v, plan, vel_mode)
+    seis, hist = fwi_forward(coeffs, plan, v.shape[0], keep_history)
+    return seis, coeffs, vstat, hist
+
+
+@fwi.register_fake
+def _(v, plan, vel_mode, keep_history):
+    return _fake_fwi(v, plan, keep_history)
 
 
 @torch.library.custom_op(f"{LIB}::fwi_ckpt", mutates_args=())
@@ -353,161 +408,7 @@ def fwi_ckpt(v: Tensor, plan: int, vel_mode: int, K: int) -> Tuple[Tensor, Tenso
 
 @fwi_ckpt.register_fake
 def _(v, plan, vel_mode, K):
-    coeffs, vstat = _fake_coeffs(v, plan)
-    p = _plan(plan)
-    B = v.shape[0]
-    return (coeffs.new_empty(_seis_shape(p, B)), coeffs, vstat,
-            coeffs.new_empty(int(p.ckpt_sizes(B, K).ckpt) // 4))
-
-
-def _fwi_ckpt_setup(ctx, inputs, output):
-    v, plan, vel_mode, K = inputs
-    _, coeffs, vstat, ckpt = output
-    ctx.mark_non_differentiable(coeffs, vstat, ckpt)
-    ctx.set_materialize_grads(False)
-    ctx.plan, ctx.vel_mode, ctx.B, ctx.K = plan, vel_mode, v.shape[0], K
-    ctx.coeffs, ctx.vstat, ctx.ckpt = coeffs, vstat, ckpt
-
-
-def _fwi_ckpt_backward(ctx, gseis, _gc, _gv, _gk):
-    p = _plan(ctx.plan)
-    seg = _f32(p.ckpt_sizes(ctx.B, ctx.K).seg, ctx.coeffs.device)
-    gA, gk, gb = fwi_adjoint_ckpt(ctx.coeffs, ctx.ckpt, seg, gseis.contiguous(), ctx.plan, ctx.B, ctx.K)
-    ctx.ckpt = None                     # the two history buffers: released as soon as the adjoint has run
-    del seg
-    g = fwi_grad_finalize(ctx.coeffs, ctx.vstat, gA, gk, gb, ctx.plan, ctx.B, ctx.vel_mode)
-    return g, None, None, None
-
-
-fwi_ckpt.register_autograd(_fwi_ckpt_backward, setup_context=_fwi_ckpt_setup)
-
-
-# ---- caller-supplied wavelets, per model and per shot, differentiable (rdq_fwi_*_src): always the narrow chunked
-# kernels.  `w` is (B, ns, nt) fp32 with a unit last stride; a zero stride on the first or second axis (an
-# expand() of a shared wavelet) is passed on as "shared", so nothing is materialised and autograd's own expand
-# backward sums the gradient over the shared axes.
-def _source(p, w, B, gw=None):
-    if w.dim() != 3 or tuple(w.shape) != (B, p.ns, p.nt) or w.dtype != torch.float32:
-        raise ValueError(f"fwi wavelet: expected fp32 of shape {(B, p.ns, p.nt)}, got {w.dtype} {tuple(w.shape)}")
-    if w.stride(2) != 1 or w.stride(0) < 0 or w.stride(1) < 0:
-        w = w.contiguous()
-    # (the tensor is returned too: it owns the memory the struct points to)
-    return w, _hip.FwiSource(wav=w.data_ptr(), model_stride=w.stride(0), shot_stride=w.stride(1),
-                             gwav=gw.data_ptr() if gw is not None else None)
-
-
-@torch.library.custom_op(f"{LIB}::fwi_forward_src", mutates_args=())
-def fwi_forward_src(coeffs: Tensor, w: Tensor, plan: int, B: int, keep_history: bool) -> Tuple[Tensor, Tensor]:
-    """fwi_forward with the source samples w[b, s, n] instead of the plan's wavelet."""
-    p = _plan(plan)
-    _hip.require_device(coeffs, w)
-    sz = p.sizes(B)
-    w, src = _source(p, w, B)
-    seis = torch.empty(_seis_shape(p, B), dtype=torch.float32, device=coeffs.device)
-    hist = _f32(sz.history if keep_history else 0, coeffs.device)
-    ring = _f32(sz.ring, coeffs.device)
-    _hip.check(p.lib.rdq_fwi_forward_src(p.handle, B, _hip.ptr(coeffs), ctypes.byref(src), _hip.ptr(seis),
-                                         _hip.ptr(hist) if keep_history else ctypes.c_void_p(0), _hip.ptr(ring),
-                                         _hip.stream_of(coeffs)), "rdq_fwi_forward_src")
-    return seis, hist
-
-
-@fwi_forward_src.register_fake
-def _(coeffs, w, plan, B, keep_history):
-    return _fake_forward(coeffs, plan, B, keep_history)
-
-
-def _gw_alloc(p, B, want_gw, dev):
-    return torch.empty((B, p.ns, p.nt) if want_gw else (0,), dtype=torch.float32, device=dev)
-
-
-@torch.library.custom_op(f"{LIB}::fwi_adjoint_src", mutates_args=())
-def fwi_adjoint_src(coeffs: Tensor, w: Tensor, history: Tensor, dseis: Tensor, plan: int, B: int,
-                    want_gw: bool) -> Tuple[Tensor, Tensor, Tensor, Tensor]:
-    """(gA, gk, gbeta, gw): fwi_adjoint with the source samples w, and gw = d(loss)/d(w) (B, ns, nt) where
-    want_gw (else empty: the kernel is given no gwav and nothing is allocated)."""
-    p = _plan(plan)
-    _hip.require_device(coeffs, w, history, dseis)
-    sz = p.sizes(B)
-    if dseis.shape != _seis_shape(p, B) or history.numel() * 4 != sz.history:
-        raise ValueError("fwi_adjoint_src: dseis / history do not match the plan")
-    dseis = dseis.float().contiguous()
-    gw = _gw_alloc(p, B, want_gw, coeffs.device)
-    w, src = _source(p, w, B, gw if want_gw else None)
-    ring = _f32(sz.ring, coeffs.device)
-    gA = _f32(sz.gA, coeffs.device)
-    gk = torch.empty(int(sz.gk_part) // 8, dtype=torch.float64, device=coeffs.device)
-    gb = _f32(sz.gbeta, coeffs.device)
-    _hip.check(p.lib.rdq_fwi_adjoint_src(p.handle, B, _hip.ptr(coeffs), ctypes.byref(src), _hip.ptr(history),
-                                         _hip.ptr(dseis), _hip.ptr(ring), _hip.ptr(gA), _hip.ptr(gk), _hip.ptr(gb),
-                                         _hip.stream_of(coeffs)), "rdq_fwi_adjoint_src")
-    return gA, gk, gb, gw
-
-
-def _fake_adjoint_src(coeffs, plan, B, want_gw):
-    p = _plan(plan)
-    sz = p.sizes(B)
-    return (coeffs.new_empty(int(sz.gA) // 4), coeffs.new_empty(int(sz.gk_part) // 8, dtype=torch.float64),
-            coeffs.new_empty(int(sz.gbeta) // 4), coeffs.new_empty((B, p.ns, p.nt) if want_gw else (0,)))
-
-
-@fwi_adjoint_src.register_fake
-def _(coeffs, w, history, dseis, plan, B, want_gw):
-    return _fake_adjoint_src(coeffs, plan, B, want_gw)
-
-
-@torch.library.custom_op(f"{LIB}::fwi_forward_ckpt_src", mutates_args=())
-def fwi_forward_ckpt_src(coeffs: Tensor, w: Tensor, plan: int, B: int, K: int) -> Tuple[Tensor, Tensor]:
-    """fwi_forward_ckpt with the source samples w."""
-    p = _plan(plan)
-    _hip.require_device(coeffs, w)
-    cs = p.ckpt_sizes(B, K)                      # (K < 1 raises here)
-    w, src = _source(p, w, B)
-    seis = torch.empty(_seis_shape(p, B), dtype=torch.float32, device=coeffs.device)
-    ckpt = _f32(cs.ckpt, coeffs.device)
-    ring = _f32(p.sizes(B).ring, coeffs.device)
-    _hip.check(p.lib.rdq_fwi_forward_ckpt_src(p.handle, B, K, _hip.ptr(coeffs), ctypes.byref(src), _hip.ptr(seis),
-                                              _hip.ptr(ckpt), _hip.ptr(ring), _hip.stream_of(coeffs)),
-               "rdq_fwi_forward_ckpt_src")
-    return seis, ckpt
-
-
-@fwi_forward_ckpt_src.register_fake
-def _(coeffs, w, plan, B, K):
-    p = _plan(plan)
-    return coeffs.new_empty(_seis_shape(p, B)), coeffs.new_empty(int(p.ckpt_sizes(B, K).ckpt) // 4)
-
-
-@torch.library.custom_op(f"{LIB}::fwi_adjoint_ckpt_src", mutates_args=("seg",))
-def fwi_adjoint_ckpt_src(coeffs: Tensor, w: Tensor, ckpt: Tensor, seg: Tensor, dseis: Tensor, plan: int, B: int,
-                         K: int, want_gw: bool) -> Tuple[Tensor, Tensor, Tensor, Tensor]:
-    """(gA, gk, gbeta, gw): fwi_adjoint_ckpt with the source samples w (the recompute reads them again)."""
-    p = _plan(plan)
-    _hip.require_device(coeffs, w, ckpt, seg, dseis)
-    sz, cs = p.sizes(B), p.ckpt_sizes(B, K)
-    if dseis.shape != _seis_shape(p, B):
-        raise ValueError("fwi_adjoint_ckpt_src: dseis does not match the plan")
-    if ckpt.dtype != torch.float32 or seg.dtype != torch.float32 or ckpt.numel() * 4 != cs.ckpt \
-            or seg.numel() * 4 != cs.seg or not ckpt.is_contiguous() or not seg.is_contiguous():
-        raise ValueError(f"fwi_adjoint_ckpt_src: ckpt / seg must be contiguous fp32 of {cs.ckpt} / {cs.seg} bytes "
-                         f"(K = {K}), got {ckpt.numel() * ckpt.element_size()} / {seg.numel() * seg.element_size()}")
-    dseis = dseis.float().contiguous()
-    gw = _gw_alloc(p, B, want_gw, coeffs.device)
-    w, src = _source(p, w, B, gw if want_gw else None)
-    ring = _f32(sz.ring, coeffs.device)
-    gA = _f32(sz.gA, coeffs.device)
-    gk = torch.empty(int(sz.gk_part) // 8, dtype=torch.float64, device=coeffs.device)
-    gb = _f32(sz.gbeta, coeffs.device)
-    _hip.check(p.lib.rdq_fwi_adjoint_ckpt_src(p.handle, B, K, _hip.ptr(coeffs), ctypes.byref(src), _hip.ptr(ckpt),
-                                              _hip.ptr(seg), _hip.ptr(dseis), _hip.ptr(ring), _hip.ptr(gA),
-                                              _hip.ptr(gk), _hip.ptr(gb), _hip.stream_of(coeffs)),
-               "rdq_fwi_adjoint_ckpt_src")
-    return gA, gk, gb, gw
-
-
-@fwi_adjoint_ckpt_src.register_fake
-def _(coeffs, w, ckpt, seg, dseis, plan, B, K, want_gw):
-    return _fake_adjoint_src(coeffs, plan, B, want_gw)
+    return _fake_fwi(v, plan, K=K)
 
 
 @torch.library.custom_op(f"{LIB}::fwi_src", mutates_args=())
@@ -520,38 +421,7 @@ def fwi_src(v: Tensor, w: Tensor, plan: int, vel_mode: int, keep_history: bool) 
 
 @fwi_src.register_fake
 def _(v, w, plan, vel_mode, keep_history):
-    coeffs, vstat = _fake_coeffs(v, plan)
-    seis, hist = _fake_forward(coeffs, plan, v.shape[0], keep_history)
-    return seis, coeffs, vstat, hist
-
-
-def _fwi_src_setup(ctx, inputs, output):
-    v, w, plan, vel_mode, keep_history = inputs
-    _, coeffs, vstat, hist = output
-    ctx.mark_non_differentiable(coeffs, vstat, hist)
-    ctx.set_materialize_grads(False)
-    if not keep_history:
-        ctx.plan = None
-        return
-    ctx.plan, ctx.vel_mode, ctx.B = plan, vel_mode, v.shape[0]
-    ctx.coeffs, ctx.vstat, ctx.hist = coeffs, vstat, hist
-    ctx.save_for_backward(w)
-
-
-def _fwi_src_backward(ctx, gseis, _gc, _gv, _gh):
-    if ctx.plan is None:
-        raise RuntimeError("red_diffeq::fwi_src was called with keep_history=False; no gradient is available")
-    if gseis is None:
-        return None, None, None, None, None
-    (w,) = ctx.saved_tensors
-    want_v, want_w = ctx.needs_input_grad[0], ctx.needs_input_grad[1]
-    gA, gk, gb, gw = fwi_adjoint_src(ctx.coeffs, w, ctx.hist, gseis.contiguous(), ctx.plan, ctx.B, want_w)
-    ctx.hist = None
-    g = fwi_grad_finalize(ctx.coeffs, ctx.vstat, gA, gk, gb, ctx.plan, ctx.B, ctx.vel_mode) if want_v else None
-    return g, (gw if want_w else None), None, None, None
-
-
-fwi_src.register_autograd(_fwi_src_backward, setup_context=_fwi_src_setup)
+    return _fake_fwi(v, plan, keep_history)
 
 
 @torch.library.custom_op(f"{LIB}::fwi_ckpt_src", mutates_args=())
@@ -564,39 +434,52 @@ def fwi_ckpt_src(v: Tensor, w: Tensor, plan: int, vel_mode: int, K: int) -> Tupl
 
 @fwi_ckpt_src.register_fake
 def _(v, w, plan, vel_mode, K):
-    coeffs, vstat = _fake_coeffs(v, plan)
-    p = _plan(plan)
-    B = v.shape[0]
-    return (coeffs.new_empty(_seis_shape(p, B)), coeffs, vstat,
-            coeffs.new_empty(int(p.ckpt_sizes(B, K).ckpt) // 4))
+    return _fake_fwi(v, plan, K=K)
 
 
-def _fwi_ckpt_src_setup(ctx, inputs, output):
-    v, w, plan, vel_mode, K = inputs
-    _, coeffs, vstat, ckpt = output
-    ctx.mark_non_differentiable(coeffs, vstat, ckpt)
-    ctx.set_materialize_grads(False)
-    ctx.plan, ctx.vel_mode, ctx.B, ctx.K = plan, vel_mode, v.shape[0], K
-    ctx.coeffs, ctx.vstat, ctx.ckpt = coeffs, vstat, ckpt
-    ctx.save_for_backward(w)
+def _register_gradient(op, name, ckpt, src):
+    """The autograd formula of fwi{,_ckpt}{,_src}: inputs (v, [w,] plan, vel_mode, keep_history | K).  The backward
+    is the adjoint op of the same variant (looked up by name when it runs), then K4 for v; w.grad is the adjoint's gw."""
+    adjoint = "fwi_adjoint" + ("_ckpt" if ckpt else "") + ("_src" if src else "")
+
+    def setup(ctx, inputs, output):
+        v, (plan, vel_mode, last) = inputs[0], inputs[-3:]
+        _, coeffs, vstat, store = output
+        # only seis is differentiable: no zero "gradients" are materialised for the saved buffers
+        # (a zeros_like of the history would be a multi-GB fill per backward)
+        ctx.mark_non_differentiable(coeffs, vstat, store)
+        ctx.set_materialize_grads(False)
+        ctx.plan = None
+        if not ckpt and not last:           # keep_history=False
+            return
+        ctx.plan, ctx.vel_mode, ctx.B, ctx.K = plan, vel_mode, v.shape[0], last
+        ctx.coeffs, ctx.vstat, ctx.store = coeffs, vstat, store
+        if src:
+            ctx.save_for_backward(inputs[1])
+
+    def backward(ctx, gseis, _gc, _gv, _gs):
+        if ctx.plan is None:
+            raise RuntimeError(f"red_diffeq::{name} was called with keep_history=False; no gradient is available")
+        if gseis is None:                   # seis took no part in the loss: no gradient, for every variant
+            return (None,) * (5 if src else 4)
+        want_v, want_w = ctx.needs_input_grad[0], src and ctx.needs_input_grad[1]
+        args = [ctx.coeffs, *ctx.saved_tensors, ctx.store]
+        if ckpt:
+            args.append(_f32(_plan(ctx.plan).ckpt_sizes(ctx.B, ctx.K).seg, ctx.coeffs.device))
+        args += [gseis.contiguous(), ctx.plan, ctx.B] + ([ctx.K] if ckpt else []) + ([want_w] if src else [])
+        gA, gk, gb, *gw = globals()[adjoint](*args)
+        ctx.store = None                    # the history / the checkpoint store, and the segment buffer: released as
+        del args                            # soon as the adjoint has run
+        g = fwi_grad_finalize(ctx.coeffs, ctx.vstat, gA, gk, gb, ctx.plan, ctx.B, ctx.vel_mode) if want_v else None
+        return (g, gw[0] if want_w else None, None, None, None) if src else (g, None, None, None)
+
+    op.register_autograd(backward, setup_context=setup)
 
 
-def _fwi_ckpt_src_backward(ctx, gseis, _gc, _gv, _gk):
-    if gseis is None:
-        return None, None, None, None, None
-    p = _plan(ctx.plan)
-    (w,) = ctx.saved_tensors
-    want_v, want_w = ctx.needs_input_grad[0], ctx.needs_input_grad[1]
-    seg = _f32(p.ckpt_sizes(ctx.B, ctx.K).seg, ctx.coeffs.device)
-    gA, gk, gb, gw = fwi_adjoint_ckpt_src(ctx.coeffs, w, ctx.ckpt, seg, gseis.contiguous(), ctx.plan, ctx.B, ctx.K,
-                                          want_w)
-    ctx.ckpt = None
-    del seg
-    g = fwi_grad_finalize(ctx.coeffs, ctx.vstat, gA, gk, gb, ctx.plan, ctx.B, ctx.vel_mode) if want_v else None
-    return g, (gw if want_w else None), None, None, None
-
-
-fwi_ckpt_src.register_autograd(_fwi_ckpt_src_backward, setup_context=_fwi_ckpt_src_setup)
+_register_gradient(fwi, "fwi", ckpt=False, src=False)
+_register_gradient(fwi_ckpt, "fwi_ckpt", ckpt=True, src=False)
+_register_gradient(fwi_src, "fwi_src", ckpt=False, src=True)
+_register_gradient(fwi_ckpt_src, "fwi_ckpt_src", ckpt=True, src=True)
 
 
 # ---------------------------------------------------------------------------------------- U-Net

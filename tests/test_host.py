@@ -473,3 +473,34 @@ def test_k12_covers_only_the_reference_ssim():
     s = SSIM(window_size=11)
     s.window = s.window * 1.01
     assert not k12_covers(s)
+
+
+FWI_OP_SCHEMAS = {
+    "fwi": "red_diffeq::fwi(Tensor v, SymInt plan, SymInt vel_mode, bool keep_history) -> (Tensor, Tensor, Tensor, Tensor)",
+    "fwi_adjoint": "red_diffeq::fwi_adjoint(Tensor coeffs, Tensor history, Tensor dseis, SymInt plan, SymInt B) -> (Tensor, Tensor, Tensor)",
+    "fwi_adjoint_ckpt": "red_diffeq::fwi_adjoint_ckpt(Tensor coeffs, Tensor ckpt, Tensor(a2!) seg, Tensor dseis, SymInt plan, SymInt B, SymInt K) -> (Tensor, Tensor, Tensor)",
+    "fwi_adjoint_ckpt_src": "red_diffeq::fwi_adjoint_ckpt_src(Tensor coeffs, Tensor w, Tensor ckpt, Tensor(a3!) seg, Tensor dseis, SymInt plan, SymInt B, SymInt K, bool want_gw) -> (Tensor, Tensor, Tensor, Tensor)",
+    "fwi_adjoint_src": "red_diffeq::fwi_adjoint_src(Tensor coeffs, Tensor w, Tensor history, Tensor dseis, SymInt plan, SymInt B, bool want_gw) -> (Tensor, Tensor, Tensor, Tensor)",
+    "fwi_born": "red_diffeq::fwi_born(Tensor coeffs, Tensor vstat, Tensor history, Tensor dv, SymInt plan, SymInt B, SymInt vel_mode) -> Tensor",
+    "fwi_born_fused": "red_diffeq::fwi_born_fused(Tensor coeffs, Tensor vstat, Tensor dv, SymInt plan, SymInt B, SymInt vel_mode, SymInt K) -> (Tensor, Tensor, Tensor)",
+    "fwi_ckpt": "red_diffeq::fwi_ckpt(Tensor v, SymInt plan, SymInt vel_mode, SymInt K) -> (Tensor, Tensor, Tensor, Tensor)",
+    "fwi_ckpt_src": "red_diffeq::fwi_ckpt_src(Tensor v, Tensor w, SymInt plan, SymInt vel_mode, SymInt K) -> (Tensor, Tensor, Tensor, Tensor)",
+    "fwi_coeffs": "red_diffeq::fwi_coeffs(Tensor v, SymInt plan, SymInt vel_mode) -> (Tensor, Tensor)",
+    "fwi_forward": "red_diffeq::fwi_forward(Tensor coeffs, SymInt plan, SymInt B, bool keep_history) -> (Tensor, Tensor)",
+    "fwi_forward_ckpt": "red_diffeq::fwi_forward_ckpt(Tensor coeffs, SymInt plan, SymInt B, SymInt K) -> (Tensor, Tensor)",
+    "fwi_forward_ckpt_src": "red_diffeq::fwi_forward_ckpt_src(Tensor coeffs, Tensor w, SymInt plan, SymInt B, SymInt K) -> (Tensor, Tensor)",
+    "fwi_forward_src": "red_diffeq::fwi_forward_src(Tensor coeffs, Tensor w, SymInt plan, SymInt B, bool keep_history) -> (Tensor, Tensor)",
+    "fwi_grad_finalize": "red_diffeq::fwi_grad_finalize(Tensor coeffs, Tensor vstat, Tensor gA, Tensor gk, Tensor gbeta, SymInt plan, SymInt B, SymInt vel_mode) -> Tensor",
+    "fwi_src": "red_diffeq::fwi_src(Tensor v, Tensor w, SymInt plan, SymInt vel_mode, bool keep_history) -> (Tensor, Tensor, Tensor, Tensor)",
+}
+
+
+def test_fwi_op_schemas_are_unchanged():
+    """The 16 torch.ops.red_diffeq.fwi* operators are the interface FWIForward, INTEGRATION.md and callers'
+    torch.compile graphs are written against: name, argument names and order, types, the one mutated argument
+    (`seg`) and the outputs, as registered before ops.py put one implementation behind them."""
+    import red_diffeq.ops  # noqa: F401  (registers the operators; imports without a GPU)
+    ns = torch.ops.red_diffeq
+    assert sorted(n for n in dir(ns) if n.startswith("fwi")) == sorted(FWI_OP_SCHEMAS)
+    for name, schema in FWI_OP_SCHEMAS.items():
+        assert str(getattr(ns, name).default._schema) == schema, name
