@@ -432,6 +432,58 @@ int rdq_fwi_adjoint_ckpt_src(const rdq_fwi_plan *plan, int32_t B, int32_t K, con
                              const rdq_fwi_source *src, const float *ckpt, float *seg, const float *dseis,
                              float *ring, float *gA, double *gk_part, float *gbeta, hipStream_t stream);
 
+/* Encoded simultaneous sources ("supershots") and their gradient: ne wavefields per model, each fired by ALL ns
+ * sources of the plan at once, source s of supershot e with its own effective wavelet (a code E[b, e, s] times a
+ * signature, formed by the caller).  K1 / K2, their checkpointed forms and K4 for such a call.
+ *   Equations.  Wavefield (b, e) obeys the forward step as written above (rdq_fwi_born) with the source term
+ *     P_{n+1}[b, e, isz, isx[s]] += beta[b, isz, isx[s]] * weff[b, e, s, n]     for every s = 0 .. ns - 1,
+ *   weff[b, e, s, n] = wav[b * model_stride + e * enc_stride + s * source_stride + n], in ascending s and per source
+ *   in the chunked forward's fp32 order (add = beta * weff; P = P + add).  Sources that share a padded cell add one
+ *   after the other, ascending s.  Every source is injected, one whose samples are zero included: the bits do not
+ *   depend on the sparsity pattern of a code.  The receivers record as in K1.  With L_k the adjoint field of (b, e)
+ *   after step k's receiver residual (rdq_fwi_*_src above), the transposes are
+ *     gwav [b, e, s, k - 1] = L_k[b, e, isz, isx[s]] * beta[b, isz, isx[s]]       (one fp32 multiply),
+ *     gbeta[b, e, s]        = sum_k L_k[b, e, isz, isx[s]] * weff[b, e, s, k - 1]  (fp32, k = nt .. 1, as K2),
+ *   and gA, gk_part are per wavefield, exactly K2's with ns replaced by ne.
+ *   Layout.  Every per-shot buffer of the calls these mirror has ns replaced by ne: seis and dseis [B][ne][nrec][ng],
+ *   history [nt + 2][B][ne][Hp][ld], ring, gA [B][ne][Hp][ld], gk_part [B][ne][nblk], the checkpoint store and the
+ *   segment buffer.  rdq_fwi_sizes_enc / rdq_fwi_ckpt_sizes_enc give their sizes (rdq_fwi_sizes / rdq_fwi_ckpt_sizes
+ *   with ns replaced by ne), except that gbeta is float [B][ne][ns].  gwav is float [B][ne][ns][nt].
+ *   One writer per element.  The tile interiors partition the padded grid, so exactly one lane of one workgroup owns
+ *   a source cell of wavefield (b, e); it owns every source on that cell and writes their gwav and gbeta elements,
+ *   and a call runs every step k once.  gwav is stored plainly, once per element and call (overwritten, not
+ *   accumulated); gbeta is zeroed by the call and accumulated by its owner lane alone, in the order of k.  No atomics.
+ *   rdq_fwi_grad_finalize_enc is K4 for these accumulators: the ne planes of gA and of gk_part are summed in order
+ *   where K4 sums its ns planes, and source cell s takes sum_e gbeta[b, e, s] (fp32, ascending e).
+ *   The calls always run the narrow chunked kernels at rdq_fwi_set_tuning's depths and chains, whatever
+ *   rdq_fwi_set_persistent or RDQ_VARIANT_NARROW_CHUNKED say, stream-ordered on caller-owned buffers under the
+ *   one-call-in-flight rule, with the checkpoint layout of rdq_fwi_forward_ckpt; a checkpointed backward's recompute
+ *   reads the same device samples, which must be unchanged between the two calls.  seis, gwav, gA and gbeta are
+ *   bit-identical for every depth, chain count, graph setting and K.  A supershot whose samples are zero but for one
+ *   source s records rdq_fwi_forward_src's seismogram of shot s with the same samples (a zero term leaves a sum's
+ *   value unchanged), and with ne = ns and weff[b, e, s] = (e == s) w[b, s] the accumulators hold the values of
+ *   rdq_fwi_adjoint_src's, gbeta on its diagonal.  RDQ_E_INVALID for a null `enc` or `wav`, ne < 1, B < 1 or a
+ *   negative stride (and, as in the calls they mirror, a null required buffer). */
+typedef struct rdq_fwi_encoding {
+    int32_t ne;                          /* supershots per model */
+    const float *wav;                    /* device, fp32: weff[b, e, s, n] at wav[b*model_stride + e*enc_stride + s*source_stride + n] */
+    int64_t model_stride, enc_stride, source_stride;   /* in floats; 0 = shared along that axis */
+    float *gwav;                         /* adjoint calls only: float [B][ne][ns][nt] = d(loss)/d(weff), overwritten;
+                                            NULL = not wanted */
+} rdq_fwi_encoding;
+int rdq_fwi_sizes_enc(const rdq_fwi_plan *plan, int32_t B, int32_t ne, rdq_fwi_sizes_t *out);
+int rdq_fwi_ckpt_sizes_enc(const rdq_fwi_plan *plan, int32_t B, int32_t ne, int32_t K, rdq_fwi_ckpt_sizes_t *out);
+int rdq_fwi_forward_enc(const rdq_fwi_plan *plan, int32_t B, const float *coeffs, const rdq_fwi_encoding *enc,
+                        float *seis, float *history, float *ring, hipStream_t stream);
+int rdq_fwi_adjoint_enc(const rdq_fwi_plan *plan, int32_t B, const float *coeffs, const rdq_fwi_encoding *enc,
+                        const float *history, const float *dseis, float *ring, float *gA, double *gk_part,
+                        float *gbeta, hipStream_t stream);
+int rdq_fwi_forward_ckpt_enc(const rdq_fwi_plan *plan, int32_t B, int32_t K, const float *coeffs,
+                             const rdq_fwi_encoding *enc, float *seis, float *ckpt, float *ring, hipStream_t stream);
+int rdq_fwi_adjoint_ckpt_enc(const rdq_fwi_plan *plan, int32_t B, int32_t K, const float *coeffs,
+                             const rdq_fwi_encoding *enc, const float *ckpt, float *seg, const float *dseis,
+                             float *ring, float *gA, double *gk_part, float *gbeta, hipStream_t stream);
+
 /* K4: d(loss)/d(v) [B][nz][nx] (contiguous) from the accumulators: chain through
  * alpha/beta/sponge(vmin), replicate-pad fold, and (RDQ_VEL_NORMALIZED) the x1500 of the
  * denormalisation. */
@@ -439,6 +491,12 @@ int rdq_fwi_grad_finalize(const rdq_fwi_plan *plan, int32_t B, const float *coef
                           const void *vstat, const float *gA, const double *gk_part,
                           const float *gbeta, int32_t vel_mode, double *colsum, float *g_v,
                           hipStream_t stream);
+/* K4 of an encoded call (rdq_fwi_*_enc above): gA [B][ne][Hp][ld], gk_part [B][ne][nblk], gbeta [B][ne][ns].
+ * RDQ_E_INVALID for ne < 1 and whatever rdq_fwi_grad_finalize refuses. */
+int rdq_fwi_grad_finalize_enc(const rdq_fwi_plan *plan, int32_t B, int32_t ne, const float *coeffs,
+                              const void *vstat, const float *gA, const double *gk_part,
+                              const float *gbeta, int32_t vel_mode, double *colsum, float *g_v,
+                              hipStream_t stream);
 
 /* K5: L1 observation loss (red_diffeq/core/losses.py:14-41), contiguous [B][n] operands.
  * forward:  loss[b] = sum(|y - pred| * mask) / nobs[b],  nobs[b] = max(sum(mask), 1)

@@ -31,6 +31,7 @@
 #include <cstdlib>
 #include <cstring>
 #include <new>
+#include <type_traits>
 #include <vector>
 #include <initializer_list>
 #include <mutex>
@@ -301,7 +302,19 @@ struct FwdTBArgs {
     // wav[b * wms + s * wss + n] (strides in floats, 0 = shared); `w` is not read
     const float *wav;
     long long wms, wss;
+    // ENC instantiations (rdq_fwi_*_enc): g.ns counts the call's ne supershots and the kernels' `s` is the supershot
+    // e; the effective sample of source j is wav[b * wms + e * wes + j * wss + n].  A lane's sources are those of
+    // its column, src_list[src_start[gx] .. src_start[gx + 1]), ascending j (the twin of rcv_start / rcv_list).
+    // These instantiations read neither g.isx nor the samples `w`, and their three extra arguments ride there, so
+    // that the argument block (and with it the compiled text of every other instantiation) stays as it was:
+    // g.isx = the plan's source table {src_start [Wp + 1], src_list [ns]} (src_start[Wp] = the source count), and
+    // wes = the 64 bits of w[0], w[1] (enc_stride_bits / enc_stride).
 };
+
+__device__ __forceinline__ long long enc_stride(const float *w)
+{
+    return (long long)(((unsigned long long)__builtin_bit_cast(unsigned, w[1]) << 32) | __builtin_bit_cast(unsigned, w[0]));
+}
 
 // exchange two boundary rows each way between the NW waves of the workgroup
 struct Halo4 { float u2, u1, d1, d2; };
@@ -508,7 +521,13 @@ __device__ __forceinline__ void tb_t1t2(float A, float kp, float &t1, float &t2)
 // SRC: the source samples are the call's own wavelets, read from a.wav (rdq_fwi_*_src) instead of the
 // kernel-argument samples a.w of the plan's wavelet; b and s are workgroup-uniform, so the launch's T
 // samples are uniform loads, hoisted ahead of the step loop.  Same operation order either way.
-template <int T, bool GEN, bool SRC = false>
+// SRC_ENC: an encoded supershot (rdq_fwi_*_enc).  Wavefield (b, e) takes every source of the plan, each with its own
+// effective samples; a lane injects the sources of its own column on the source row(s), in ascending source index,
+// each as add = beta * w; P = P + add.  The T samples of the lane's first source are per-lane loads hoisted like
+// SRC_CALL's, in the waves that hold the source row; a column's further sources (rare: smulti, wave-uniform, like
+// rmulti) are read in the step.  Every source is injected, a zero sample included.
+constexpr int SRC_PLAN = 0, SRC_CALL = 1, SRC_ENC = 2;
+template <int T, bool GEN, int SRC = SRC_PLAN>
 __global__ __launch_bounds__(64 * TB_NW) void k_fwd_tb(FwdTBArgs a)
 {
     constexpr int H = 2 * T, IW = 64 - 2 * H, IH = TB_RH - 2 * H;
@@ -526,7 +545,7 @@ __global__ __launch_bounds__(64 * TB_NW) void k_fwd_tb(FwdTBArgs a)
     const size_t so = (size_t)bs * g.slice;
     const float *AL = a.coeffs + (size_t)b * g.slice;
     const float *T1p = AL + g.cstride, *T2p = AL + 2 * g.cstride;
-    const int isx = g.isx[s];
+    const int isx = SRC == SRC_ENC ? gx : g.isx[s];      // ENC: every column's own cell; its sources below
     float A[TB_R], C1[TB_R], C2v[TB_R], P0[TB_R], P1[TB_R];
     int rofs[TB_R];                 // wave-uniform row offsets gz*ld
     unsigned rin = 0;               // wave-uniform: row is interior and inside the domain
@@ -552,7 +571,18 @@ __global__ __launch_bounds__(64 * TB_NW) void k_fwd_tb(FwdTBArgs a)
     unsigned smask = 0;
 #pragma unroll
     for (int r = 0; r < TB_R; ++r) if (wrapn(uz0 + r, g.Hp) == g.isz) smask |= 1u << r;
-    const bool scol = gx == isx;
+    int es0 = 0, es1 = 0, esrc0 = -1;   // ENC: this column's sources, src_list[es0 .. es1), and the first of them
+    bool smulti = false;                // wave-uniform: a column with several sources
+    const int *src_list = nullptr;
+    if constexpr (SRC == SRC_ENC) {
+        const int *src_start = g.isx;
+        src_list = g.isx + g.Wp + 1;
+        if (smask) { es0 = src_start[gx]; es1 = src_start[gx + 1]; }
+        if (es0 < es1) esrc0 = src_list[es0];
+        smulti = __any(es1 - es0 > 1);
+    }
+    (void)esrc0; (void)smulti; (void)src_list;
+    const bool scol = SRC == SRC_ENC ? es0 < es1 : gx == isx;
     const float bsrc = (smask != 0) ? a.coeffs[4 * g.cstride + (size_t)b * g.slice + (size_t)g.isz * g.ld + isx] : 0.0f;
     const int rs = (rrow >= 0) ? g.rcv_start[gx] : 0, re = (rrow >= 0) ? g.rcv_start[gx + 1] : 0;
     // this lane's (usually only) receiver, read once: a per-step index load would put an L2 round
@@ -560,11 +590,19 @@ __global__ __launch_bounds__(64 * TB_NW) void k_fwd_tb(FwdTBArgs a)
     const int rcv0 = rs < re ? g.rcv_list[rs] : -1;
     const bool rmulti = __any(re - rs > 1);               // wave-uniform: a column with several receivers
     float ws[T];                    // SRC: w[b, s, n0 .. n0 + nsteps - 1]
-    if constexpr (SRC) {
+    const float *wpe = nullptr;     // ENC: w[b, e, 0, n0]
+    if constexpr (SRC == SRC_CALL) {
         const float *wp = a.wav + (size_t)b * a.wms + (size_t)s * a.wss + a.n0;
 #pragma unroll
         for (int t = 0; t < T; ++t) ws[t] = t < a.nsteps ? wp[t] : 0.0f;
     }
+    if constexpr (SRC == SRC_ENC) {
+        wpe = a.wav + (size_t)b * a.wms + (size_t)s * enc_stride(a.w) + a.n0;
+        const float *wp = wpe + (size_t)(scol ? esrc0 : 0) * a.wss;
+#pragma unroll
+        for (int t = 0; t < T; ++t) ws[t] = (scol && t < a.nsteps) ? wp[t] : 0.0f;
+    }
+    (void)wpe;
     (void)ws;
 #pragma unroll
     for (int t = 0; t < T; ++t) {
@@ -585,9 +623,17 @@ __global__ __launch_bounds__(64 * TB_NW) void k_fwd_tb(FwdTBArgs a)
             for (int r = 0; r < TB_R; ++r)
                 if ((smask & (1u << r)) && scol) {
                     float wt;
-                    if constexpr (SRC) wt = ws[t]; else wt = a.w[t];
+                    if constexpr (SRC != SRC_PLAN) wt = ws[t]; else wt = a.w[t];
                     const float add = bsrc * wt; prv[r] = prv[r] + add;
                 }
+            if constexpr (SRC == SRC_ENC) {
+                if (smulti)
+                    for (int j = es0 + 1; j < es1; ++j) {
+                        const float add = bsrc * wpe[(size_t)src_list[j] * a.wss + t];
+#pragma unroll
+                        for (int r = 0; r < TB_R; ++r) if (smask & (1u << r)) prv[r] = prv[r] + add;
+                    }
+            }
         }
         const int n = a.n0 + t;
         if (a.hist && xin) {
@@ -641,6 +687,8 @@ struct AdjTBArgs {
     long long wms, wss;
     float *gwav;
     int nt;
+    // ENC instantiations (rdq_fwi_*_enc): g.isx and w[0], w[1] as in FwdTBArgs; gbeta is [B][ne][nsrc] and gwav
+    // [B][ne][nsrc][nt], nsrc = the plan's source count
 };
 
 // Adjoint with the same register-region blocking, walking k = k0, k0-1, ...:
@@ -656,7 +704,12 @@ struct AdjTBArgs {
 // stored by the lane that owns the source cell (gbl).  The tiles' interiors partition the grid, so exactly one
 // lane of one workgroup owns that cell, and a call runs every k once: one writer per element, a plain store,
 // no atomics and no dependence on what gwav held.
-template <int T, bool SRC = false>
+// SRC_ENC: wavefield (b, e) of an encoded call.  The lane that owns a source cell owns every source j on it:
+//   gwav[b, e, j, k-1] = L_k(cell) beta(cell),   gbeta[b, e, j] += L_k(cell) w[b, e, j, k-1],
+// the cell's first source through the registers above (gbacc, ws), its further ones (smulti, rare) with the sample
+// read in the step and a read-modify-write of their gbeta element by this one lane, in the same order of k.  One
+// owner lane per cell and every k run once: one writer per element of gwav and gbeta, as above.
+template <int T, int SRC = SRC_PLAN>
 __global__ __launch_bounds__(64 * TB_NW, 4) void k_adj_tb(AdjTBArgs a)
 {
     constexpr int H = 2 * T, IW = 64 - 2 * H, IH = TB_RH - 2 * H;
@@ -676,7 +729,7 @@ __global__ __launch_bounds__(64 * TB_NW, 4) void k_adj_tb(AdjTBArgs a)
     const size_t so = (size_t)bs * g.slice;
     const float *AL = a.coeffs + (size_t)b * g.slice;
     const float *KAp = AL + 3 * g.cstride;
-    const int isx = g.isx[s];
+    const int isx = SRC == SRC_ENC ? gx : g.isx[s];      // ENC: every column's own cell; its sources below
     float A[TB_R], L0[TB_R], L1[TB_R];   // temp1/temp2 are re-derived from A and K (tb_t1t2)
     float gal[TB_R], kal[TB_R];          // gA_s accumulators and the sponge coefficient K, in registers
     int rofs[TB_R];
@@ -697,25 +750,47 @@ __global__ __launch_bounds__(64 * TB_NW, 4) void k_adj_tb(AdjTBArgs a)
         if (gz == g.igz) rmask |= 1u << r;
         gal[r] = ((rin & (1u << r)) && xin) ? a.gA[so + o] : 0.0f;
     }
-    const bool scol = gx == isx;
+    // ENC: this column's sources are src_list[es0 .. es1); kept past this prologue are only the first one's index
+    // and its slot in gbeta / gwav, (b, e, source) (the rare further sources are looked up again where they are used:
+    // the depth-4 kernel has no register to spare at 4 workgroups per CU)
+    int es0 = 0, es1 = 0, esrc0 = 0, gslot = 0;
+    bool smulti = false;                // wave-uniform: a column with several sources
+    if constexpr (SRC == SRC_ENC) {
+        const int *src_start = g.isx, *src_list = g.isx + g.Wp + 1;
+        if (smask & rin) { es0 = src_start[gx]; es1 = src_start[gx + 1]; }
+        if (es0 < es1) { esrc0 = src_list[es0]; gslot = bs * src_start[g.Wp] + esrc0; }
+        smulti = __any(es1 - es0 > 1);
+    }
+    (void)smulti; (void)gslot;
+    const bool scol = SRC == SRC_ENC ? es0 < es1 : gx == isx;
     // residual of this lane's column: one receiver's dseis, or several receivers' folded sum
     const int rcv0 = rmask ? g.rlane[gx] : -1;
     const float *DSb = a.dseis + (size_t)bs * g.nrec * g.dstride;
     // gbeta of this shot accumulates in a register over the launch's steps (same order as a
     // per-step read-modify-write of a.gbeta[bs]), stored once at the end
     const bool gbl = (smask & rin) && scol && xin;       // the source cell is this lane's own cell
-    float gbacc = gbl ? a.gbeta[bs] : 0.0f;
+    // (ENC: this lane's element is its first source's of wavefield (b, e))
+    float gbacc;
+    if constexpr (SRC == SRC_ENC) gbacc = gbl ? a.gbeta[gslot] : 0.0f;
+    else gbacc = gbl ? a.gbeta[bs] : 0.0f;
     float ws[T];                    // SRC: w[b, s, k0 - 1 - t]
     float bsrc = 0.0f;              // SRC: beta at the source cell, on the lane that owns it and stores gwav
     bool gw = false;
-    if constexpr (SRC) {
+    if constexpr (SRC == SRC_CALL) {
         const float *wp = a.wav + (size_t)b * a.wms + (size_t)s * a.wss + a.k0 - 1;
 #pragma unroll
         for (int t = 0; t < T; ++t) ws[t] = t < a.nsteps ? wp[-t] : 0.0f;
         gw = gbl && a.gwav;
         if (gw) bsrc = a.coeffs[4 * g.cstride + (size_t)b * g.slice + (size_t)g.isz * g.ld + isx];
     }
-    (void)ws; (void)bsrc; (void)gw;
+    if constexpr (SRC == SRC_ENC) {
+        const float *wp = a.wav + (size_t)b * a.wms + (size_t)s * enc_stride(a.w) + (size_t)esrc0 * a.wss + a.k0 - 1;
+#pragma unroll
+        for (int t = 0; t < T; ++t) ws[t] = (gbl && t < a.nsteps) ? wp[-t] : 0.0f;
+        gw = gbl && a.gwav;
+        if (gw) bsrc = a.coeffs[4 * g.cstride + (size_t)b * g.slice + (size_t)g.isz * g.ld + isx];
+    }
+    (void)ws; (void)bsrc; (void)gw; (void)esrc0;
     double ksum = 0.0;
     // history P_{k-1} on the rows whose stencil the interior needs: HBM stream, prefetched one
     // step ahead so its latency hides under the previous step
@@ -790,17 +865,38 @@ __global__ __launch_bounds__(64 * TB_NW, 4) void k_adj_tb(AdjTBArgs a)
                 ksum += (double)kk;                                                             // fp64 sum
                 if ((smask & (1u << r)) && scol) {
                     float wt;
-                    if constexpr (SRC) wt = ws[t]; else wt = a.w[t];
+                    if constexpr (SRC != SRC_PLAN) wt = ws[t]; else wt = a.w[t];
                     const float gb = l * wt; gbacc = gbacc + gb;
                 }
             }
         }
-        if constexpr (SRC) {   // one store per step, not one per row: the source row's L_k picked by the wave-uniform mask
+        if constexpr (SRC == SRC_CALL) {   // one store per step, not one per row: the source row's L_k picked by the wave-uniform mask
             if (gw) {
                 float ls = 0.0f;
 #pragma unroll
                 for (int r = 0; r < TB_R; ++r) if (smask & rin & (1u << r)) ls = prv[r];
                 a.gwav[(size_t)bs * a.nt + (k - 1)] = ls * bsrc;
+            }
+        }
+        if constexpr (SRC == SRC_ENC) {    // the same store for the cell's first source, then its further sources
+            if (gw || (smulti && gbl)) {
+                float ls = 0.0f;
+#pragma unroll
+                for (int r = 0; r < TB_R; ++r) if (smask & rin & (1u << r)) ls = prv[r];
+                const float gwv = ls * bsrc;
+                if (gw) a.gwav[(size_t)gslot * a.nt + (k - 1)] = gwv;
+                if (smulti && gbl) {
+                    const int *src_start = g.isx, *src_list = g.isx + g.Wp + 1;
+                    const float *wk = a.wav + (size_t)b * a.wms + (size_t)s * enc_stride(a.w) + (k - 1);
+                    const int slot0 = bs * src_start[g.Wp];
+                    for (int j = src_start[gx] + 1; j < src_start[gx + 1]; ++j) {
+                        const int sj = src_list[j];
+                        const float gb = ls * wk[(size_t)sj * a.wss];
+                        float *gbj = a.gbeta + (slot0 + sj);
+                        *gbj = *gbj + gb;
+                        if (gw) a.gwav[(size_t)(slot0 + sj) * a.nt + (k - 1)] = gwv;
+                    }
+                }
             }
         }
     }
@@ -815,7 +911,8 @@ __global__ __launch_bounds__(64 * TB_NW, 4) void k_adj_tb(AdjTBArgs a)
                 a.gA[o] = gal[r];
             }
     }
-    if (gbl) a.gbeta[bs] = gbacc;
+    if constexpr (SRC == SRC_ENC) { if (gbl) a.gbeta[gslot] = gbacc; }
+    else if (gbl) a.gbeta[bs] = gbacc;
     // deterministic workgroup reduction of the sponge-coefficient partial sum
     const int tid = threadIdx.x;
     red[tid] = ksum;
@@ -3102,6 +3199,10 @@ struct FinArgs {
     double *colsum;   // [B][Hp][nx]
     float *out;       // [B][nz][nx]
 };
+// rdq_fwi_grad_finalize_enc: ne supershots; gA [B][ne][Hp][ld], gk_part [B][ne][nblk], gbeta [B][ne][ns]
+struct FinEncArgs : FinArgs {
+    int ne;
+};
 
 // Stage 1: per padded row z and model column ix, sum g_vpad over the padded columns that
 // replicate ix (F.pad replicate backward).  g_vpad is formed per point exactly as autograd
@@ -3110,13 +3211,19 @@ struct FinArgs {
 // One workgroup per padded row (z, b): every padded cell's d(loss)/d(v_pad) (fp64) into LDS, all
 // cells in parallel; then the replicate-pad fold along x: interior columns take their own cell,
 // the two edge columns sum their nbc+1-wide strips (one wave each, fixed-order shuffle tree).
+// ENC: the accumulators of an encoded call.  The ne wavefield planes of gA and gk_part are summed in order where
+// the plain call sums its ns shot planes, and source s takes sum_e gbeta[b, e, s] (fp32, ascending e).
 constexpr int FIN_MAXW = 4096;
-__global__ __launch_bounds__(256) void k_fin_rows(FinArgs p)
+template <class Args>
+__global__ __launch_bounds__(256) void k_fin_rows(Args p)
 {
+    constexpr bool ENC = std::is_same_v<Args, FinEncArgs>;
+    int nw;                                           // wavefields per model
+    if constexpr (ENC) nw = p.ne; else nw = p.ns;
     __shared__ double gv_s[FIN_MAXW];
     const int z = blockIdx.x, b = blockIdx.y;
     const size_t ro = (size_t)b * p.slice + (size_t)z * p.ld;
-    const float *GA = p.gA + (size_t)b * p.ns * p.slice + (size_t)z * p.ld;   // [B][ns][Hp][ld]
+    const float *GA = p.gA + (size_t)b * nw * p.slice + (size_t)z * p.ld;   // [B][ns][Hp][ld]
     const float *V = p.coeffs + 5 * p.cstride + ro;
     const int amz = (int)(p.amin[b] / p.nx), amx = (int)(p.amin[b] - (int64_t)amz * p.nx);
     const int apz = amz == 0 ? 0 : amz + p.nbc, apx = amx == 0 ? 0 : amx + p.nbc;
@@ -3125,7 +3232,7 @@ __global__ __launch_bounds__(256) void k_fin_rows(FinArgs p)
     // loads (ns * nblk round trips)
     __shared__ double gk_s[256];
     if (z == apz) {
-        const int cnt = p.ns * p.nblk, per = (cnt + 255) / 256;
+        const int cnt = nw * p.nblk, per = (cnt + 255) / 256;
         const double *GK = p.gk_part + (size_t)b * cnt;
         double acc = 0.0;
         const int j0 = threadIdx.x * per, j1 = min(cnt, j0 + per);
@@ -3144,14 +3251,14 @@ __global__ __launch_bounds__(256) void k_fin_rows(FinArgs p)
         float ga = 0.0f;
         {   // shots in order (the oracle's order); the loads are issued 4 at a time
             int s = 0;
-            for (; s + 4 <= p.ns; s += 4) {
+            for (; s + 4 <= nw; s += 4) {
                 float v[4];
 #pragma unroll
                 for (int u = 0; u < 4; ++u) v[u] = GA[(size_t)(s + u) * p.slice + x];
 #pragma unroll
                 for (int u = 0; u < 4; ++u) ga = ga + v[u];
             }
-            for (; s < p.ns; ++s) ga = ga + GA[(size_t)s * p.slice + x];
+            for (; s < nw; ++s) ga = ga + GA[(size_t)s * p.slice + x];
         }
         float t = ga * (2.0f * a1); t = t / p.dx; t = t * p.dt;
         double gv = (double)t;
@@ -3159,7 +3266,12 @@ __global__ __launch_bounds__(256) void k_fin_rows(FinArgs p)
             for (int s = 0; s < p.ns; ++s)
                 if (p.isx[s] == x) {
                     const float b1 = V[x] * p.dt;
-                    float u = p.gbeta[b * p.ns + s] * (2.0f * b1); u = u * p.dt;
+                    float gb;
+                    if constexpr (ENC) {
+                        gb = 0.0f;
+                        for (int e = 0; e < p.ne; ++e) gb = gb + p.gbeta[((size_t)b * p.ne + e) * p.ns + s];
+                    } else gb = p.gbeta[b * p.ns + s];
+                    float u = gb * (2.0f * b1); u = u * p.dt;
                     gv += (double)u;
                 }
         }
@@ -3372,11 +3484,12 @@ __global__ __launch_bounds__(256) void k_smooth_bwd(int kind, int H, int W, cons
 // ======================================================================================= plan
 struct GraphEntry {
     int kind;                 // 0 fwd-history, 1 fwd-ring, 2 adjoint, 3 fwd-checkpoint, 4 adjoint-checkpoint, 5 born,
-                              // 6 fused forward + born; + 8: the same pass with the call's own wavelets
+                              // 6 fused forward + born; + 8: the same pass with the call's own wavelets;
+                              // + 16: with an encoding (rdq_fwi_*_enc)
     int B;
     int K;                    // checkpoint interval (kinds 3, 4, 6; else 0): it shapes the launch sequence
     const void *ptrs[10];     // the call's buffers; a per-call source adds its wav and gwav
-    long long strides[2];     // and its two wavelet strides (else 0)
+    long long strides[4];     // and its wavelet strides (else 0); an encoding: its three strides and ne
     hipGraphExec_t exec;
     uint64_t last_use;
 };
@@ -3396,6 +3509,7 @@ struct rdq_fwi_plan {
     std::vector<float> wavf;
     int Hp, Wp, ld, nrec;
     int *d_isx = nullptr, *d_rcv_start = nullptr, *d_rcv_list = nullptr;
+    int *d_src_table = nullptr; // sources by padded column, as the receivers: {src_start [Wp + 1], src_list [ns]} (FwdTBArgs)
     int *d_rlane = nullptr;     // [Wp] adjoint residual index per column (receiver id, or folded column)
     int *d_colx = nullptr;      // [ncolr] padded column of each receiver column (fold)
     int ncolr = 0;              // columns holding a receiver
@@ -3451,20 +3565,22 @@ int tiles_x(int Wp, int T) { return (Wp + (64 - 4 * T) - 1) / (64 - 4 * T); }
 int tiles_y(int Hp, int T) { return (Hp + (TB_RH - 4 * T) - 1) / (TB_RH - 4 * T); }
 
 
-TBGeo tb_geo(const rdq_fwi_plan *p, int B)
+// nwf: wavefields per model, the plan's shots or an encoded call's supershots
+TBGeo tb_geo(const rdq_fwi_plan *p, int B, int nwf)
 {
     TBGeo g;
-    g.B = B; g.ns = p->g.ns; g.Hp = p->Hp; g.Wp = p->Wp; g.ld = p->ld;
+    g.B = B; g.ns = nwf; g.Hp = p->Hp; g.Wp = p->Wp; g.ld = p->ld;
     g.isz = p->g.isz; g.igz = p->g.igz; g.ng = p->g.ng; g.nrec = p->nrec; g.st = p->g.sample_temporal;
     g.slice = (size_t)p->Hp * p->ld;
     g.cstride = (size_t)B * g.slice;
     g.level = (size_t)B * g.ns * g.slice;
     g.isx = p->d_isx; g.rcv_start = p->d_rcv_start; g.rcv_list = p->d_rcv_list;
     g.rlane = p->d_rlane; g.dstride = p->rmulti ? p->ncolr : p->g.ng;
-    g.s_off = 0; g.ns_grp = p->g.ns;
-    g.sl_off = 0; g.nsl = B * p->g.ns;
+    g.s_off = 0; g.ns_grp = nwf;
+    g.sl_off = 0; g.nsl = B * nwf;
     return g;
 }
+TBGeo tb_geo(const rdq_fwi_plan *p, int B) { return tb_geo(p, B, p->g.ns); }
 
 // Shots split into `chains` groups, each a dependent chain of launches on its own stream, forked
 // from and joined back into `st` with events (inside graph capture this records parallel graph
@@ -3474,11 +3590,12 @@ TBGeo tb_geo(const rdq_fwi_plan *p, int B)
 // launches fill the other's tail rounds: configs[4] forward 54.7 -> 49.0-50.0 ms, adjoint 93.8 ->
 // 91.0-91.6; 3 / 4 / 8 chains 51.7 / 53.9 / 58.0 and 93.1 / 95.1 / 101.2; profiles/r5/configs4_chains.jsonl),
 // one for the 64-column kernels.
-int chain_count(const rdq_fwi_plan *p, bool wide)
+int chain_count(const rdq_fwi_plan *p, bool wide, int nwf)
 {
     const int c = p->chains > 0 ? p->chains : (wide ? 2 : 1);
-    return std::max(1, std::min(c, p->g.ns));
+    return std::max(1, std::min(c, nwf));
 }
+int chain_count(const rdq_fwi_plan *p, bool wide) { return chain_count(p, wide, p->g.ns); }
 int chain_count(const rdq_fwi_plan *p) { return chain_count(p, p->wide); }
 
 // Default depth of the wide chunked adjoint, measured at configs[4] (profiles/r5/configs4_wide_adj_depth.jsonl):
@@ -3676,12 +3793,23 @@ KernelRef<AdjTBArgs> adj_tb_kernel(int T)
 KernelRef<FwdTBArgs> fwd_tb_src_kernel(int T, bool gen)
 {
     return with_depth<TB_MAXT>(T, [&](auto t) -> KernelRef<FwdTBArgs> {
-        return {gen ? k_fwd_tb<t(), true, true> : k_fwd_tb<t(), false, true>, 64 * TB_NW};
+        return {gen ? k_fwd_tb<t(), true, SRC_CALL> : k_fwd_tb<t(), false, SRC_CALL>, 64 * TB_NW};
     });
 }
 KernelRef<AdjTBArgs> adj_tb_src_kernel(int T)
 {
-    return with_depth<TB_MAXT>(T, [](auto t) -> KernelRef<AdjTBArgs> { return {k_adj_tb<t(), true>, 64 * TB_NW}; });
+    return with_depth<TB_MAXT>(T, [](auto t) -> KernelRef<AdjTBArgs> { return {k_adj_tb<t(), SRC_CALL>, 64 * TB_NW}; });
+}
+// and with an encoding (rdq_fwi_*_enc)
+KernelRef<FwdTBArgs> fwd_tb_enc_kernel(int T, bool gen)
+{
+    return with_depth<TB_MAXT>(T, [&](auto t) -> KernelRef<FwdTBArgs> {
+        return {gen ? k_fwd_tb<t(), true, SRC_ENC> : k_fwd_tb<t(), false, SRC_ENC>, 64 * TB_NW};
+    });
+}
+KernelRef<AdjTBArgs> adj_tb_enc_kernel(int T)
+{
+    return with_depth<TB_MAXT>(T, [](auto t) -> KernelRef<AdjTBArgs> { return {k_adj_tb<t(), SRC_ENC>, 64 * TB_NW}; });
 }
 KernelRef<BornTBArgs> born_tb_kernel(int T, bool gen)
 {
@@ -4187,11 +4315,13 @@ struct Launch {
 // passes that always run the narrow (64-column) kernels at the forward's narrow depth
 bool narrow_pass(Pass pass) { return pass == Pass::born || pass == Pass::fwd_born; }
 
-std::vector<Launch> chunked_schedule(const rdq_fwi_plan *p, int B, Pass pass, const CkptPlan &cp, bool src = false)
+// src: a call with its own wavelets or an encoding (narrow kernels); nwf: its wavefields per model, 0 = the plan's shots
+std::vector<Launch> chunked_schedule(const rdq_fwi_plan *p, int B, Pass pass, const CkptPlan &cp, bool src = false,
+                                     int nwf = 0)
 {
     const bool wide = p->wide && !narrow_pass(pass) && !src;
     const int Tf = wide ? wide_fwd_depth(p) : p->fwd_T, Ta = wide ? wide_adj_depth(p) : p->adj_T;
-    const int S = chain_count(p, wide), ns = p->g.ns;
+    const int ns = nwf > 0 ? nwf : p->g.ns, S = chain_count(p, wide, ns);
     std::vector<Launch> sched;
     auto add = [&](Launch::Kind kind, int c, int sg, int first, int nsteps, LevelPair in, LevelPair out) {
         Launch l{};
@@ -4271,6 +4401,8 @@ struct ChunkBufs {
     const float *dwork;              // born: the perturbation workspace (`seis` is then the linearised record)
     float *dseis_out;                // fwd_born: the linearised record (`seis` is the forward's)
     const rdq_fwi_source *src;       // the call's own wavelets (rdq_fwi_*_src), or nullptr: the plan's
+    const rdq_fwi_encoding *enc;     // the call's encoding (rdq_fwi_*_enc): ne wavefields per model, every buffer
+                                     // above with ns replaced by ne, gbeta [B][ne][ns]; or nullptr
 };
 
 // What every time-loop launch sets the same way in its kernel arguments: the launch's shots and tile grid, and the
@@ -4283,17 +4415,24 @@ void launch_geo_and_wavelet(TBGeo &g, float (&w)[N], const Launch &l, const std:
     for (int t = 0; t < N; ++t) w[t] = t < l.nsteps ? wavf[adj ? l.first - 1 - t : l.first + t] : 0.0f;
 }
 
+// an encoded launch's supershot stride, as the bits of w[0], w[1] (FwdTBArgs; the kernels' enc_stride)
+void enc_stride_bits(float *w, long long stride)
+{
+    std::memcpy(w, &stride, sizeof(stride));
+}
+
 int enqueue_chunked(rdq_fwi_plan *p, int B, Pass pass, int K, const ChunkBufs &b, hipStream_t st)
 {
-    const bool src = b.src != nullptr;
-    const std::vector<Launch> sched = chunked_schedule(p, B, pass, ckpt_plan(p, K), src);
+    const bool enc = b.enc != nullptr, src = b.src != nullptr || enc;
+    const int ns = enc ? b.enc->ne : p->g.ns;        // wavefields per model
+    const std::vector<Launch> sched = chunked_schedule(p, B, pass, ckpt_plan(p, K), src, ns);
     FwdTBArgs f{};
     AdjTBArgs a{};
     BornTBArgs d{};
     FwdBornTBArgs u{};
-    f.g = a.g = d.g = u.g = tb_geo(p, B);
+    f.g = a.g = d.g = u.g = tb_geo(p, B, ns);
     const size_t L = a.g.level, slice = a.g.slice;
-    const int S = chain_count(p, p->wide && !narrow_pass(pass) && !src), ns = p->g.ns, nblk_alloc = gk_blocks(p);
+    const int S = chain_count(p, p->wide && !narrow_pass(pass) && !src, ns), nblk_alloc = gk_blocks(p);
     const bool adjoint = pass == Pass::adj_hist || pass == Pass::adj_ckpt;
     if (adjoint) {   // the gk_part one-writer invariant, on every adjoint launch, before anything is enqueued
         GkWriters writers((size_t)B * ns, nblk_alloc);
@@ -4306,7 +4445,7 @@ int enqueue_chunked(rdq_fwi_plan *p, int B, Pass pass, int K, const ChunkBufs &b
     if (adjoint)
         RDQ_TRY(zero_regions({{b.ring, 4 * L * sizeof(float)}, {b.gA, L * sizeof(float)},
                               {b.gk, (size_t)B * ns * nblk_alloc * sizeof(double)},
-                              {b.gbeta, (size_t)B * ns * sizeof(float)}}, st));
+                              {b.gbeta, (size_t)B * ns * (enc ? p->g.ns : 1) * sizeof(float)}}, st));
     else if (pass == Pass::fwd_hist) RDQ_TRY(zero_regions({{b.hist, 2 * L * sizeof(float)}}, st));
     else RDQ_TRY(zero_regions({{b.ring, (pass == Pass::fwd_born ? 8 : 4) * L * sizeof(float)}}, st));   // P, and dP in 4-7
     f.coeffs = a.coeffs = d.coeffs = u.coeffs = b.coeffs;
@@ -4321,7 +4460,12 @@ int enqueue_chunked(rdq_fwi_plan *p, int B, Pass pass, int K, const ChunkBufs &b
     f.seis = b.seis; f.hist = b.hist;
     a.hist = b.hist; a.dseis = b.dseis; a.gA = b.gA; a.gk_part = b.gk; a.gbeta = b.gbeta;
     a.nblk = nblk_alloc;
-    if (src) {
+    if (enc) {
+        f.wav = a.wav = b.enc->wav;
+        f.wms = a.wms = b.enc->model_stride; f.wss = a.wss = b.enc->source_stride;
+        f.g.isx = a.g.isx = p->d_src_table;          // (the source table; the supershot stride goes with each launch's w below)
+        a.gwav = b.enc->gwav; a.nt = p->g.nt;
+    } else if (src) {
         f.wav = a.wav = b.src->wav;
         f.wms = a.wms = b.src->model_stride; f.wss = a.wss = b.src->shot_stride;
         a.gwav = b.src->gwav; a.nt = p->g.nt;
@@ -4341,11 +4485,14 @@ int enqueue_chunked(rdq_fwi_plan *p, int B, Pass pass, int K, const ChunkBufs &b
                                (size_t)ns * slice, (size_t)l.s_off * slice, run, B);
         } else if (l.kind == Launch::fwd) {
             launch_geo_and_wavelet(f.g, f.w, l, p->wavf);
+            if (enc) enc_stride_bits(f.w, b.enc->enc_stride);
             f.ns_sh = l.ns_sh; f.spw = l.spw;
             f.n0 = l.first; f.nsteps = l.nsteps; f.hbase = l.hbase;
             f.in_prev = level(l.in, 0); f.in_cur = level(l.in, 1);
             f.out_prev = level(l.out, 0); f.out_cur = level(l.out, 1);
-            launch_kernel(src ? fwd_tb_src_kernel(p->fwd_T, p->fwd_gen) : chunk_fwd_kernel(p, l.nsteps), l.grid, cs, f);
+            launch_kernel(enc   ? fwd_tb_enc_kernel(p->fwd_T, p->fwd_gen)
+                          : src ? fwd_tb_src_kernel(p->fwd_T, p->fwd_gen)
+                                : chunk_fwd_kernel(p, l.nsteps), l.grid, cs, f);
         } else if (l.kind == Launch::born) {
             launch_geo_and_wavelet(d.g, d.w, l, p->wavf);
             d.n0 = l.first; d.nsteps = l.nsteps;
@@ -4362,11 +4509,13 @@ int enqueue_chunked(rdq_fwi_plan *p, int B, Pass pass, int K, const ChunkBufs &b
             launch_kernel(fwd_born_tb_kernel(p->fwd_T, p->fwd_gen), l.grid, cs, u);
         } else {
             launch_geo_and_wavelet(a.g, a.w, l, p->wavf);
+            if (enc) enc_stride_bits(a.w, b.enc->enc_stride);
             a.ns_sh = l.ns_sh; a.spw = l.spw;
             a.k0 = l.first; a.nsteps = l.nsteps; a.hbase = l.hbase;
             a.in_l1 = level(l.in, 0); a.in_l2 = level(l.in, 1);
             a.out_l1 = level(l.out, 0); a.out_l2 = level(l.out, 1);
-            launch_kernel(src ? adj_tb_src_kernel(p->adj_T) : chunk_adj_kernel(p, l.nsteps), l.grid, cs, a);
+            launch_kernel(enc ? adj_tb_enc_kernel(p->adj_T) : src ? adj_tb_src_kernel(p->adj_T) : chunk_adj_kernel(p, l.nsteps),
+                          l.grid, cs, a);
         }
     }
     RDQ_CHECK(hipGetLastError());
@@ -4394,11 +4543,12 @@ void set_knob(rdq_fwi_plan *p, T &knob, T value)
 
 // Several receivers in one padded column: their residuals folded per column into the ring's tail
 // (k_rcv_fold), which the adjoint kernels then read in place of the caller's dseis.
-int fold_residuals(const rdq_fwi_plan *p, int B, const float *&dseis, float *ring, hipStream_t st)
+int fold_residuals(const rdq_fwi_plan *p, int B, const float *&dseis, float *ring, hipStream_t st, int nwf = 0)
 {
     if (!p->rmulti) return 0;
-    float *fold = ring + 8 * (size_t)B * p->g.ns * p->Hp * p->ld;
-    const size_t rows = (size_t)B * p->g.ns * p->nrec, n = rows * p->ncolr;
+    const size_t ns = nwf > 0 ? nwf : p->g.ns;       // wavefields per model
+    float *fold = ring + 8 * (size_t)B * ns * p->Hp * p->ld;
+    const size_t rows = (size_t)B * ns * p->nrec, n = rows * p->ncolr;
     hipLaunchKernelGGL(k_rcv_fold, dim3((unsigned)std::min<size_t>((n + 255) / 256, 4096)), dim3(256), 0, st,
                        dseis, fold, p->d_colx, p->d_rcv_start, p->d_rcv_list, p->g.ng, p->ncolr, rows);
     RDQ_CHECK(hipGetLastError());
@@ -4408,16 +4558,20 @@ int fold_residuals(const rdq_fwi_plan *p, int B, const float *&dseis, float *rin
 
 template <class F>
 int run_cached(rdq_fwi_plan *p, int kind, int B, std::initializer_list<const void *> key, hipStream_t st, F &&launch,
-               int K = 0, const rdq_fwi_source *src = nullptr)
+               int K = 0, const rdq_fwi_source *src = nullptr, const rdq_fwi_encoding *enc = nullptr)
 {
     if (!p->graphs) return launch(st);
     const void *k[10] = {nullptr};
-    long long ks[2] = {0, 0};
+    long long ks[4] = {0, 0, 0, 0};
     int n = 0;
     for (const void *v : key) k[n++] = v;
     if (src) { k[8] = src->wav; k[9] = src->gwav; ks[0] = src->model_stride; ks[1] = src->shot_stride; }
+    if (enc) {
+        k[8] = enc->wav; k[9] = enc->gwav;
+        ks[0] = enc->model_stride; ks[1] = enc->source_stride; ks[2] = enc->enc_stride; ks[3] = enc->ne;
+    }
     for (auto &e : p->cache)
-        if (e.kind == kind && e.B == B && e.K == K && std::equal(k, k + 10, e.ptrs) && std::equal(ks, ks + 2, e.strides)) {
+        if (e.kind == kind && e.B == B && e.K == K && std::equal(k, k + 10, e.ptrs) && std::equal(ks, ks + 4, e.strides)) {
             e.last_use = ++p->tick;
             RDQ_CHECK(hipGraphLaunch(e.exec, st));
             return 0;
@@ -4432,7 +4586,7 @@ int run_cached(rdq_fwi_plan *p, int kind, int B, std::initializer_list<const voi
     GraphEntry e{};
     e.kind = kind; e.B = B; e.K = K;
     std::copy(k, k + 10, e.ptrs);
-    std::copy(ks, ks + 2, e.strides);
+    std::copy(ks, ks + 4, e.strides);
     const hipError_t ie = hipGraphInstantiate(&e.exec, graph, nullptr, nullptr, 0);
     (void)hipGraphDestroy(graph);
     RDQ_CHECK(ie);
@@ -4507,7 +4661,16 @@ int rdq_fwi_plan_create(const rdq_fwi_geom *geom, rdq_fwi_plan **out)
     }
     p->ncolr = (int)colx.size();
     for (int c = 0; c < p->ncolr; ++c) rlane[colx[c]] = p->rmulti ? c : order[start[colx[c]]];
+    // sources grouped by column the same way (encoded calls: a lane injects its column's sources in ascending index)
+    std::vector<int> sorder(geom->ns), sstart(p->Wp + 1, 0);
+    for (int j = 0; j < geom->ns; ++j) sorder[j] = j;
+    std::stable_sort(sorder.begin(), sorder.end(), [&](int a, int b) { return p->isx[a] < p->isx[b]; });
+    for (int j = 0; j < geom->ns; ++j) sstart[p->isx[j] + 1]++;
+    for (int x = 0; x < p->Wp; ++x) sstart[x + 1] += sstart[x];
     hipError_t e = hipMalloc(&p->d_isx, sizeof(int) * geom->ns);
+    sstart.insert(sstart.end(), sorder.begin(), sorder.end());
+    if (e == hipSuccess) e = hipMalloc(&p->d_src_table, sizeof(int) * sstart.size());
+    if (e == hipSuccess) e = hipMemcpy(p->d_src_table, sstart.data(), sizeof(int) * sstart.size(), hipMemcpyHostToDevice);
     if (e == hipSuccess) e = hipMalloc(&p->d_rcv_start, sizeof(int) * (p->Wp + 1));
     if (e == hipSuccess) e = hipMalloc(&p->d_rcv_list, sizeof(int) * geom->ng);
     if (e == hipSuccess) e = hipMemcpy(p->d_isx, p->isx.data(), sizeof(int) * geom->ns, hipMemcpyHostToDevice);
@@ -4540,6 +4703,7 @@ int rdq_fwi_plan_destroy(rdq_fwi_plan *p)
     if (p->d_isx) (void)hipFree(p->d_isx);
     if (p->d_rcv_start) (void)hipFree(p->d_rcv_start);
     if (p->d_rcv_list) (void)hipFree(p->d_rcv_list);
+    if (p->d_src_table) (void)hipFree(p->d_src_table);
     if (p->d_rlane) (void)hipFree(p->d_rlane);
     if (p->d_colx) (void)hipFree(p->d_colx);
     if (p->d_wav) (void)hipFree(p->d_wav);
@@ -4828,10 +4992,10 @@ int rdq_fwi_debug_words(rdq_fwi_plan *p, uint32_t out[32])
     return 0;
 }
 
-int rdq_fwi_sizes(const rdq_fwi_plan *p, int32_t B, rdq_fwi_sizes_t *o)
+// buffer sizes for nwf wavefields per model (the plan's shots, or an encoded call's supershots); gbeta is sized by the caller
+static void sizes_for(const rdq_fwi_plan *p, int32_t B, size_t ns, rdq_fwi_sizes_t *o)
 {
-    if (!p || !o || B < 1) return RDQ_E_INVALID;
-    const size_t slice = (size_t)p->Hp * p->ld, ns = p->g.ns;
+    const size_t slice = (size_t)p->Hp * p->ld;
     o->Hp = p->Hp; o->Wp = p->Wp; o->ld = p->ld; o->nrec = p->nrec;
     o->coeffs = (6 * (size_t)B * slice + (size_t)B * p->g.nz * p->g.nx + B + 4) * sizeof(float);
     o->vstat = (size_t)B * (sizeof(float) + sizeof(int64_t)) + 16;
@@ -4843,6 +5007,20 @@ int rdq_fwi_sizes(const rdq_fwi_plan *p, int32_t B, rdq_fwi_sizes_t *o)
     o->gk_part = (size_t)B * ns * gk_blocks(p) * sizeof(double);
     o->gbeta = (size_t)B * ns * sizeof(float);
     o->colsum = (size_t)B * p->Hp * p->g.nx * sizeof(double);
+}
+
+int rdq_fwi_sizes(const rdq_fwi_plan *p, int32_t B, rdq_fwi_sizes_t *o)
+{
+    if (!p || !o || B < 1) return RDQ_E_INVALID;
+    sizes_for(p, B, (size_t)p->g.ns, o);
+    return 0;
+}
+
+int rdq_fwi_sizes_enc(const rdq_fwi_plan *p, int32_t B, int32_t ne, rdq_fwi_sizes_t *o)
+{
+    if (!p || !o || B < 1 || ne < 1) return RDQ_E_INVALID;
+    sizes_for(p, B, (size_t)ne, o);
+    o->gbeta = (size_t)B * ne * p->g.ns * sizeof(float);   // [B][ne][ns]
     return 0;
 }
 
@@ -4889,16 +5067,20 @@ static bool source_ok(const rdq_fwi_source *src)
 {
     return src && src->wav && src->model_stride >= 0 && src->shot_stride >= 0;
 }
+static bool encoding_ok(const rdq_fwi_encoding *enc)
+{
+    return enc && enc->wav && enc->ne >= 1 && enc->model_stride >= 0 && enc->enc_stride >= 0 && enc->source_stride >= 0;
+}
 
 // K1, with the plan's wavelet (src == nullptr) or the call's own (always the narrow chunked kernels)
 static int forward_call(rdq_fwi_plan *p, int32_t B, const float *coeffs, const rdq_fwi_source *src, float *seis,
-                        float *hist, float *ring, hipStream_t st)
+                        float *hist, float *ring, hipStream_t st, const rdq_fwi_encoding *enc = nullptr)
 {
     if (!p || !coeffs || !seis || (!hist && !ring) || B < 1) return RDQ_E_INVALID;
     std::lock_guard<std::mutex> lk(p->mu);
     RDQ_TRY(plan_enter(p, st));
     int per = 0;
-    if (const int nw = src ? 0 : persistent_nw(p, B, false, &per)) {
+    if (const int nw = src || enc ? 0 : persistent_nw(p, B, false, &per)) {
         if (!ring) return RDQ_E_INVALID;   // the persistent kernel's hand-off granules live in `ring`
         // direct launch (one kernel + memsets per shot group: nothing for a graph to amortise; the
         // arrival counters of pt_assign are zeroed by a stream-ordered memset right before it)
@@ -4906,10 +5088,10 @@ static int forward_call(rdq_fwi_plan *p, int32_t B, const float *coeffs, const r
     }
     // chunked: the store-all schedule, writing the history or (no-grad) ping-ponging in the ring
     ChunkBufs b{};
-    b.coeffs = coeffs; b.seis = seis; b.hist = hist; b.ring = ring; b.src = src;
-    return run_cached(p, (hist ? 0 : 1) + (src ? 8 : 0), B, {coeffs, seis, hist, ring}, st, [&](hipStream_t s) {
+    b.coeffs = coeffs; b.seis = seis; b.hist = hist; b.ring = ring; b.src = src; b.enc = enc;
+    return run_cached(p, (hist ? 0 : 1) + (src ? 8 : 0) + (enc ? 16 : 0), B, {coeffs, seis, hist, ring}, st, [&](hipStream_t s) {
         return enqueue_chunked(p, B, hist ? Pass::fwd_hist : Pass::fwd_ring, p->g.nt, b, s);
-    }, 0, src);
+    }, 0, src, enc);
 }
 
 int rdq_fwi_forward(const rdq_fwi_plan *pc, int32_t B, const float *coeffs, float *seis, float *hist,
@@ -4925,22 +5107,29 @@ int rdq_fwi_forward_src(const rdq_fwi_plan *pc, int32_t B, const float *coeffs, 
     return forward_call(const_cast<rdq_fwi_plan *>(pc), B, coeffs, src, seis, hist, ring, st);
 }
 
+int rdq_fwi_forward_enc(const rdq_fwi_plan *pc, int32_t B, const float *coeffs, const rdq_fwi_encoding *enc,
+                        float *seis, float *hist, float *ring, hipStream_t st)
+{
+    if (!encoding_ok(enc)) return RDQ_E_INVALID;
+    return forward_call(const_cast<rdq_fwi_plan *>(pc), B, coeffs, nullptr, seis, hist, ring, st, enc);
+}
+
 static int adjoint_call(rdq_fwi_plan *p, int32_t B, const float *coeffs, const rdq_fwi_source *src,
                         const float *hist, const float *dseis, float *ring, float *gA, double *gk, float *gbeta,
-                        hipStream_t st)
+                        hipStream_t st, const rdq_fwi_encoding *enc = nullptr)
 {
     if (!p || !coeffs || !hist || !dseis || !ring || !gA || !gk || !gbeta || B < 1) return RDQ_E_INVALID;
     std::lock_guard<std::mutex> lk(p->mu);
     RDQ_TRY(plan_enter(p, st));
-    RDQ_TRY(fold_residuals(p, B, dseis, ring, st));
+    RDQ_TRY(fold_residuals(p, B, dseis, ring, st, enc ? enc->ne : 0));
     int per = 0;
-    if (const int nw = src ? 0 : persistent_nw(p, B, true, &per))
+    if (const int nw = src || enc ? 0 : persistent_nw(p, B, true, &per))
         return launch_adjoint_pt(p, B, nw, per, coeffs, hist, dseis, ring, gA, gk, gbeta, st);
     ChunkBufs b{};
     b.coeffs = coeffs; b.hist = const_cast<float *>(hist); b.ring = ring; b.dseis = dseis;
-    b.gA = gA; b.gk = gk; b.gbeta = gbeta; b.src = src;
-    return run_cached(p, 2 + (src ? 8 : 0), B, {coeffs, hist, dseis, ring, gA, gk, gbeta}, st,
-                      [&](hipStream_t s) { return enqueue_chunked(p, B, Pass::adj_hist, p->g.nt, b, s); }, 0, src);
+    b.gA = gA; b.gk = gk; b.gbeta = gbeta; b.src = src; b.enc = enc;
+    return run_cached(p, 2 + (src ? 8 : 0) + (enc ? 16 : 0), B, {coeffs, hist, dseis, ring, gA, gk, gbeta}, st,
+                      [&](hipStream_t s) { return enqueue_chunked(p, B, Pass::adj_hist, p->g.nt, b, s); }, 0, src, enc);
 }
 
 int rdq_fwi_adjoint(const rdq_fwi_plan *pc, int32_t B, const float *coeffs, const float *hist,
@@ -4955,6 +5144,14 @@ int rdq_fwi_adjoint_src(const rdq_fwi_plan *pc, int32_t B, const float *coeffs, 
 {
     if (!source_ok(src)) return RDQ_E_INVALID;
     return adjoint_call(const_cast<rdq_fwi_plan *>(pc), B, coeffs, src, hist, dseis, ring, gA, gk, gbeta, st);
+}
+
+int rdq_fwi_adjoint_enc(const rdq_fwi_plan *pc, int32_t B, const float *coeffs, const rdq_fwi_encoding *enc,
+                        const float *hist, const float *dseis, float *ring, float *gA, double *gk, float *gbeta,
+                        hipStream_t st)
+{
+    if (!encoding_ok(enc)) return RDQ_E_INVALID;
+    return adjoint_call(const_cast<rdq_fwi_plan *>(pc), B, coeffs, nullptr, hist, dseis, ring, gA, gk, gbeta, st, enc);
 }
 
 // perturbation workspace: dam [B][nz][nx], ratio [B], dbeta [B][ns], oscale [B], dmax [B] (k_dcoeffs)
@@ -5018,15 +5215,27 @@ int rdq_fwi_born_fused(const rdq_fwi_plan *pc, int32_t B, int32_t K, const float
                       [&](hipStream_t s) { return enqueue_chunked(p, B, Pass::fwd_born, Ke, b, s); }, Ke);
 }
 
-int rdq_fwi_ckpt_sizes(const rdq_fwi_plan *p, int32_t B, int32_t K, rdq_fwi_ckpt_sizes_t *o)
+static void ckpt_sizes_for(const rdq_fwi_plan *p, int32_t B, size_t ns, int32_t K, rdq_fwi_ckpt_sizes_t *o)
 {
-    if (!p || !o || B < 1 || K < 1) return RDQ_E_INVALID;
     const CkptPlan cp = ckpt_plan(p, K);
-    const size_t level = (size_t)B * p->g.ns * p->Hp * p->ld * sizeof(float);
+    const size_t level = (size_t)B * ns * p->Hp * p->ld * sizeof(float);
     o->nseg = cp.nseg;
     o->seg_levels = cp.K + 2;
     o->ckpt = 2 * (size_t)(cp.nseg - 1) * level;
     o->seg = (size_t)(cp.K + 2) * level;
+}
+
+int rdq_fwi_ckpt_sizes(const rdq_fwi_plan *p, int32_t B, int32_t K, rdq_fwi_ckpt_sizes_t *o)
+{
+    if (!p || !o || B < 1 || K < 1) return RDQ_E_INVALID;
+    ckpt_sizes_for(p, B, (size_t)p->g.ns, K, o);
+    return 0;
+}
+
+int rdq_fwi_ckpt_sizes_enc(const rdq_fwi_plan *p, int32_t B, int32_t ne, int32_t K, rdq_fwi_ckpt_sizes_t *o)
+{
+    if (!p || !o || B < 1 || ne < 1 || K < 1) return RDQ_E_INVALID;
+    ckpt_sizes_for(p, B, (size_t)ne, K, o);
     return 0;
 }
 
@@ -5044,17 +5253,18 @@ int rdq_fwi_ckpt_info(rdq_fwi_plan *p, int32_t B, int32_t K, int32_t out[4])
 }
 
 static int forward_ckpt_call(rdq_fwi_plan *p, int32_t B, int32_t K, const float *coeffs, const rdq_fwi_source *src,
-                             float *seis, float *ckpt, float *ring, hipStream_t st)
+                             float *seis, float *ckpt, float *ring, hipStream_t st,
+                             const rdq_fwi_encoding *enc = nullptr)
 {
     if (!p || !coeffs || !seis || !ring || B < 1 || K < 1) return RDQ_E_INVALID;
     if (!ckpt && ckpt_plan(p, K).nseg > 1) return RDQ_E_INVALID;
     std::lock_guard<std::mutex> lk(p->mu);
     RDQ_TRY(plan_enter(p, st));
     ChunkBufs b{};
-    b.coeffs = coeffs; b.seis = seis; b.ckpt = ckpt; b.ring = ring; b.src = src;
-    return run_cached(p, 3 + (src ? 8 : 0), B, {coeffs, seis, ckpt, ring}, st,
+    b.coeffs = coeffs; b.seis = seis; b.ckpt = ckpt; b.ring = ring; b.src = src; b.enc = enc;
+    return run_cached(p, 3 + (src ? 8 : 0) + (enc ? 16 : 0), B, {coeffs, seis, ckpt, ring}, st,
                       [&](hipStream_t s) { return enqueue_chunked(p, B, Pass::fwd_ring, K, b, s); }, ckpt_plan(p, K).K,
-                      src);
+                      src, enc);
 }
 
 int rdq_fwi_forward_ckpt(const rdq_fwi_plan *pc, int32_t B, int32_t K, const float *coeffs, float *seis,
@@ -5070,21 +5280,28 @@ int rdq_fwi_forward_ckpt_src(const rdq_fwi_plan *pc, int32_t B, int32_t K, const
     return forward_ckpt_call(const_cast<rdq_fwi_plan *>(pc), B, K, coeffs, src, seis, ckpt, ring, st);
 }
 
+int rdq_fwi_forward_ckpt_enc(const rdq_fwi_plan *pc, int32_t B, int32_t K, const float *coeffs,
+                             const rdq_fwi_encoding *enc, float *seis, float *ckpt, float *ring, hipStream_t st)
+{
+    if (!encoding_ok(enc)) return RDQ_E_INVALID;
+    return forward_ckpt_call(const_cast<rdq_fwi_plan *>(pc), B, K, coeffs, nullptr, seis, ckpt, ring, st, enc);
+}
+
 static int adjoint_ckpt_call(rdq_fwi_plan *p, int32_t B, int32_t K, const float *coeffs, const rdq_fwi_source *src,
                              const float *ckpt, float *seg, const float *dseis, float *ring, float *gA, double *gk,
-                             float *gbeta, hipStream_t st)
+                             float *gbeta, hipStream_t st, const rdq_fwi_encoding *enc = nullptr)
 {
     if (!p || !coeffs || !seg || !dseis || !ring || !gA || !gk || !gbeta || B < 1 || K < 1) return RDQ_E_INVALID;
     if (!ckpt && ckpt_plan(p, K).nseg > 1) return RDQ_E_INVALID;
     std::lock_guard<std::mutex> lk(p->mu);
     RDQ_TRY(plan_enter(p, st));
-    RDQ_TRY(fold_residuals(p, B, dseis, ring, st));
+    RDQ_TRY(fold_residuals(p, B, dseis, ring, st, enc ? enc->ne : 0));
     ChunkBufs b{};
     b.coeffs = coeffs; b.hist = seg; b.ckpt = const_cast<float *>(ckpt); b.ring = ring; b.dseis = dseis;
-    b.gA = gA; b.gk = gk; b.gbeta = gbeta; b.src = src;
-    return run_cached(p, 4 + (src ? 8 : 0), B, {coeffs, ckpt, seg, dseis, ring, gA, gk, gbeta}, st,
+    b.gA = gA; b.gk = gk; b.gbeta = gbeta; b.src = src; b.enc = enc;
+    return run_cached(p, 4 + (src ? 8 : 0) + (enc ? 16 : 0), B, {coeffs, ckpt, seg, dseis, ring, gA, gk, gbeta}, st,
                       [&](hipStream_t s) { return enqueue_chunked(p, B, Pass::adj_ckpt, K, b, s); }, ckpt_plan(p, K).K,
-                      src);
+                      src, enc);
 }
 
 int rdq_fwi_adjoint_ckpt(const rdq_fwi_plan *pc, int32_t B, int32_t K, const float *coeffs, const float *ckpt,
@@ -5104,27 +5321,53 @@ int rdq_fwi_adjoint_ckpt_src(const rdq_fwi_plan *pc, int32_t B, int32_t K, const
                              st);
 }
 
-int rdq_fwi_grad_finalize(const rdq_fwi_plan *p, int32_t B, const float *coeffs, const void *vstat,
-                          const float *gA, const double *gk, const float *gbeta, int32_t vel_mode,
-                          double *colsum, float *out, hipStream_t st)
+int rdq_fwi_adjoint_ckpt_enc(const rdq_fwi_plan *pc, int32_t B, int32_t K, const float *coeffs,
+                             const rdq_fwi_encoding *enc, const float *ckpt, float *seg, const float *dseis, float *ring,
+                             float *gA, double *gk, float *gbeta, hipStream_t st)
+{
+    if (!encoding_ok(enc)) return RDQ_E_INVALID;
+    return adjoint_ckpt_call(const_cast<rdq_fwi_plan *>(pc), B, K, coeffs, nullptr, ckpt, seg, dseis, ring, gA, gk,
+                             gbeta, st, enc);
+}
+
+// K4 of the plain call (ne == 0) or of an encoded one
+static int finalize_call(const rdq_fwi_plan *p, int32_t B, int32_t ne, const float *coeffs, const void *vstat,
+                         const float *gA, const double *gk, const float *gbeta, int32_t vel_mode,
+                         double *colsum, float *out, hipStream_t st)
 {
     if (!p || !coeffs || !vstat || !gA || !gk || !gbeta || !colsum || !out || B < 1 ||
         (vel_mode != 0 && vel_mode != 1))
         return RDQ_E_INVALID;
     float *vmin; int64_t *amin;
     vstat_ptrs(vstat, B, &vmin, &amin);
-    FinArgs a;
+    FinEncArgs a;
     a.B = B; a.ns = p->g.ns; a.nz = p->g.nz; a.nx = p->g.nx; a.nbc = p->g.nbc; a.Hp = p->Hp; a.Wp = p->Wp;
     a.ld = p->ld; a.isz = p->g.isz; a.nblk = gk_blocks(p); a.dt = p->g.dt; a.dx = p->g.dx;
     a.scale = vel_mode == 0 ? 1500.0 : 1.0;
     a.slice = (size_t)p->Hp * p->ld; a.cstride = (size_t)B * a.slice;
     a.coeffs = coeffs; a.gA = gA; a.gbeta = gbeta; a.vmin = vmin; a.amin = amin; a.gk_part = gk;
-    a.isx = p->d_isx; a.colsum = colsum; a.out = out;
+    a.isx = p->d_isx; a.colsum = colsum; a.out = out; a.ne = ne;
     if (p->Wp > FIN_MAXW) return RDQ_E_INVALID;
-    hipLaunchKernelGGL(k_fin_rows, dim3(p->Hp, B), dim3(256), 0, st, a);
+    if (ne) hipLaunchKernelGGL(k_fin_rows<FinEncArgs>, dim3(p->Hp, B), dim3(256), 0, st, a);
+    else hipLaunchKernelGGL(k_fin_rows<FinArgs>, dim3(p->Hp, B), dim3(256), 0, st, static_cast<const FinArgs &>(a));
     hipLaunchKernelGGL(k_fin_cols, dim3((p->g.nz * p->g.nx + 255) / 256, B), dim3(256), 0, st, a);
     RDQ_CHECK(hipGetLastError());
     return 0;
+}
+
+int rdq_fwi_grad_finalize(const rdq_fwi_plan *p, int32_t B, const float *coeffs, const void *vstat,
+                          const float *gA, const double *gk, const float *gbeta, int32_t vel_mode,
+                          double *colsum, float *out, hipStream_t st)
+{
+    return finalize_call(p, B, 0, coeffs, vstat, gA, gk, gbeta, vel_mode, colsum, out, st);
+}
+
+int rdq_fwi_grad_finalize_enc(const rdq_fwi_plan *p, int32_t B, int32_t ne, const float *coeffs, const void *vstat,
+                              const float *gA, const double *gk, const float *gbeta, int32_t vel_mode,
+                              double *colsum, float *out, hipStream_t st)
+{
+    if (ne < 1) return RDQ_E_INVALID;
+    return finalize_call(p, B, ne, coeffs, vstat, gA, gk, gbeta, vel_mode, colsum, out, st);
 }
 
 size_t rdq_l1_partial_bytes(int32_t B, int64_t n)

@@ -44,6 +44,12 @@ class FwiSource(ctypes.Structure):
     _fields_ = [("wav", c_void_p), ("model_stride", c_int64), ("shot_stride", c_int64), ("gwav", c_void_p)]
 
 
+class FwiEncoding(ctypes.Structure):
+    """struct rdq_fwi_encoding."""
+    _fields_ = [("ne", c_int32), ("wav", c_void_p), ("model_stride", c_int64), ("enc_stride", c_int64),
+                ("source_stride", c_int64), ("gwav", c_void_p)]
+
+
 class ConvDesc(ctypes.Structure):
     """struct rdq_conv_desc."""
     _fields_ = [(n, c_int32) for n in ("B", "cin1", "cin2", "H", "W", "cout", "kh", "kw", "pad", "in_mode")]
@@ -105,6 +111,18 @@ SIGNATURES = {
                                            c_void_p, c_void_p, c_void_p]),
     "rdq_fwi_adjoint_ckpt_src": (c_int32, [c_void_p, c_int32, c_int32, c_void_p, ctypes.POINTER(FwiSource), c_void_p,
                                            c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p]),
+    "rdq_fwi_sizes_enc": (c_int32, [c_void_p, c_int32, c_int32, ctypes.POINTER(FwiSizes)]),
+    "rdq_fwi_ckpt_sizes_enc": (c_int32, [c_void_p, c_int32, c_int32, c_int32, ctypes.POINTER(FwiCkptSizes)]),
+    "rdq_fwi_forward_enc": (c_int32, [c_void_p, c_int32, c_void_p, ctypes.POINTER(FwiEncoding), c_void_p, c_void_p,
+                                      c_void_p, c_void_p]),
+    "rdq_fwi_adjoint_enc": (c_int32, [c_void_p, c_int32, c_void_p, ctypes.POINTER(FwiEncoding), c_void_p, c_void_p,
+                                      c_void_p, c_void_p, c_void_p, c_void_p, c_void_p]),
+    "rdq_fwi_forward_ckpt_enc": (c_int32, [c_void_p, c_int32, c_int32, c_void_p, ctypes.POINTER(FwiEncoding), c_void_p,
+                                           c_void_p, c_void_p, c_void_p]),
+    "rdq_fwi_adjoint_ckpt_enc": (c_int32, [c_void_p, c_int32, c_int32, c_void_p, ctypes.POINTER(FwiEncoding), c_void_p,
+                                           c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p]),
+    "rdq_fwi_grad_finalize_enc": (c_int32, [c_void_p, c_int32, c_int32, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p,
+                                            c_int32, c_void_p, c_void_p, c_void_p]),
     "rdq_fwi_born_sizes": (c_int32, [c_void_p, c_int32, ctypes.POINTER(c_size_t)]),
     "rdq_fwi_dcoeffs": (c_int32, [c_void_p, c_int32, c_void_p, ctypes.POINTER(c_int64), c_int32, c_void_p, c_void_p,
                                   c_void_p, c_void_p]),

@@ -28,6 +28,12 @@ torch.compile see them as ordinary operators instead of opaque ctypes calls.
         fwi / fwi_ckpt with the call's own wavelets w (B, ns, nt), differentiable in v and in w
         (FWIForward.forward(v, wavelet=...)); built on fwi_forward_src / fwi_adjoint_src /
         fwi_forward_ckpt_src / fwi_adjoint_ckpt_src (rdq_fwi_*_src), whose adjoints also return gw = d loss / d w
+    red_diffeq::enc_fwi(v, weff, plan, vel_mode, keep_history) / enc_fwi_ckpt(v, weff, plan, vel_mode, K)
+        encoded supershots: ne wavefields per model, each fired by all ns sources with the effective wavelets
+        weff (B, ne, ns, nt); seis (B, ne, nrec, ng), differentiable in v and in weff
+        (FWIForward.forward(v, encoding=E)); built on enc_fwi_forward / enc_fwi_adjoint / enc_fwi_forward_ckpt /
+        enc_fwi_adjoint_ckpt / enc_fwi_grad_finalize (rdq_fwi_*_enc).  (Named enc_fwi*, not fwi*_enc: the set of
+        fwi* operators is pinned by the host tests.)
   U-Net (include/red_diffeq_unet.h)
     conv2d_mfma, conv2d_rms, conv2d_gn_silu, conv2d_bf16_gn_silu, conv2d_bf16_gn_silu_out, conv2d_gn_silu_sc, conv2d_gn_silu_lsm, conv2d_gn_silu_out, unet_head,
     gn_silu, rmsnorm, linear, time_mlp, linear_silu_multi, sinusoidal_emb, linear_attn, linear_attn_block, attn,
@@ -97,8 +103,17 @@ def _(v, plan, vel_mode):
             v.new_empty(int(sz.vstat), dtype=torch.uint8))
 
 
-def _seis_shape(p, B):
-    return (B, p.ns, p.sizes(B).nrec, p.ng)
+def _seis_shape(p, B, ne=None):
+    return (B, p.ns if ne is None else ne, p.sizes(B).nrec, p.ng)
+
+
+def _sizes(p, B, ne=None):
+    """rdq_fwi_sizes, or (ne: an encoded call's supershots per model) rdq_fwi_sizes_enc."""
+    return p.sizes(B) if ne is None else p.sizes_enc(B, ne)
+
+
+def _ckpt_sizes(p, B, K, ne=None):
+    return p.ckpt_sizes(B, K) if ne is None else p.ckpt_sizes_enc(B, ne, K)
 
 
 def _fake_coeffs(v, plan):
@@ -106,20 +121,24 @@ def _fake_coeffs(v, plan):
     return v.new_empty(int(sz.coeffs) // 4, dtype=torch.float32), v.new_empty(int(sz.vstat), dtype=torch.uint8)
 
 
-def _fake_forward(coeffs, plan, B, keep_history=False, K=None):
+def _fake_forward(coeffs, plan, B, keep_history=False, K=None, ne=None):
     """(seis, store): store = the history (K None; empty unless keep_history) or the checkpoint store for K."""
     p = _plan(plan)
-    nbytes = p.ckpt_sizes(B, K).ckpt if K is not None else (p.sizes(B).history if keep_history else 0)
-    return coeffs.new_empty(_seis_shape(p, B)), coeffs.new_empty(int(nbytes) // 4)
+    nbytes = _ckpt_sizes(p, B, K, ne).ckpt if K is not None else (_sizes(p, B, ne).history if keep_history else 0)
+    return coeffs.new_empty(_seis_shape(p, B, ne)), coeffs.new_empty(int(nbytes) // 4)
 
 
-def _fake_adjoint(coeffs, plan, B, want_gw=None):
-    """The accumulators (gA, gk, gbeta), and with want_gw given (the _src ops) also gw."""
+def _gw_shape(p, B, ne=None):
+    return (B, p.ns, p.nt) if ne is None else (B, ne, p.ns, p.nt)
+
+
+def _fake_adjoint(coeffs, plan, B, want_gw=None, ne=None):
+    """The accumulators (gA, gk, gbeta), and with want_gw given (the _src and enc_ ops) also gw."""
     p = _plan(plan)
-    sz = p.sizes(B)
+    sz = _sizes(p, B, ne)
     acc = (coeffs.new_empty(int(sz.gA) // 4), coeffs.new_empty(int(sz.gk_part) // 8, dtype=torch.float64),
            coeffs.new_empty(int(sz.gbeta) // 4))
-    return acc if want_gw is None else acc + (coeffs.new_empty((B, p.ns, p.nt) if want_gw else (0,)),)
+    return acc if want_gw is None else acc + (coeffs.new_empty(_gw_shape(p, B, ne) if want_gw else (0,)),)
 
 
 # Caller-supplied wavelets, per model and per shot, differentiable (rdq_fwi_*_src): always the narrow chunked
@@ -136,17 +155,36 @@ def _source(p, w, B, gw=None):
                              gwav=gw.data_ptr() if gw is not None else None)
 
 
-def _run_forward(coeffs, plan, B, keep_history=False, K=None, w=None):
-    """The one forward behind fwi_forward{,_ckpt}{,_src}: rdq_fwi_forward{,_ckpt}{,_src}.  K: checkpoints every K
-    steps instead of a history; w: the call's own wavelets.  Returns (seis, history | ckpt)."""
+# Encoded supershots (rdq_fwi_*_enc): `weff` is (B, ne, ns, nt) fp32 with a unit last stride; zero strides (expanded
+# axes) are passed on as "shared", as _source does.
+def _encoding(p, weff, B, gw=None):
+    if weff.dim() != 4 or weff.shape[0] != B or weff.shape[1] < 1 or tuple(weff.shape[2:]) != (p.ns, p.nt) \
+            or weff.dtype != torch.float32:
+        raise ValueError(f"fwi encoding: expected fp32 effective wavelets of shape {(B, 'ne', p.ns, p.nt)}, got "
+                         f"{weff.dtype} {tuple(weff.shape)}")
+    if weff.stride(3) != 1 or min(weff.stride()[:3]) < 0:
+        weff = weff.contiguous()
+    return weff, _hip.FwiEncoding(ne=weff.shape[1], wav=weff.data_ptr(), model_stride=weff.stride(0),
+                                  enc_stride=weff.stride(1), source_stride=weff.stride(2),
+                                  gwav=gw.data_ptr() if gw is not None else None)
+
+
+def _run_forward(coeffs, plan, B, keep_history=False, K=None, w=None, enc=False):
+    """The one forward behind fwi_forward{,_ckpt}{,_src} and enc_fwi_forward{,_ckpt}: rdq_fwi_forward{,_ckpt}{,_src,
+    _enc}.  K: checkpoints every K steps instead of a history; w: the call's own wavelets, or (enc) its effective
+    wavelets (B, ne, ns, nt).  Returns (seis, history | ckpt)."""
     p = _plan(plan)
     _hip.require_device(coeffs, w)
-    sz = p.sizes(B)
-    nstore = p.ckpt_sizes(B, K).ckpt if K is not None else (sz.history if keep_history else 0)   # (K < 1 raises here)
-    entry = "rdq_fwi_forward" + ("_ckpt" if K is not None else "") + ("_src" if w is not None else "")
-    if w is not None:
+    ne = None
+    if enc:
+        w, src = _encoding(p, w, B)
+        ne = w.shape[1]
+    sz = _sizes(p, B, ne)
+    nstore = _ckpt_sizes(p, B, K, ne).ckpt if K is not None else (sz.history if keep_history else 0)   # (K < 1 raises here)
+    entry = "rdq_fwi_forward" + ("_ckpt" if K is not None else "") + ("_enc" if enc else "_src" if w is not None else "")
+    if w is not None and not enc:
         w, src = _source(p, w, B)
-    seis = torch.empty(_seis_shape(p, B), dtype=torch.float32, device=coeffs.device)
+    seis = torch.empty(_seis_shape(p, B, ne), dtype=torch.float32, device=coeffs.device)
     store = _f32(nstore, coeffs.device)
     ring = _f32(sz.ring, coeffs.device)
     args = [p.handle, B] + ([K] if K is not None else []) + [_hip.ptr(coeffs)]
@@ -157,20 +195,23 @@ def _run_forward(coeffs, plan, B, keep_history=False, K=None, w=None):
     return seis, store
 
 
-def _run_adjoint(op, coeffs, dseis, plan, B, history=None, ckpt=None, seg=None, K=None, w=None, want_gw=False):
-    """The one adjoint behind fwi_adjoint{,_ckpt}{,_src}: rdq_fwi_adjoint{,_ckpt}{,_src} over a stored `history`, or
-    (K) over the checkpoint store `ckpt` with every segment recomputed into the scratch `seg`.  `op` names the public
-    op in error messages.  Returns (gA, gk, gbeta, gw); gw is empty unless want_gw."""
+def _run_adjoint(op, coeffs, dseis, plan, B, history=None, ckpt=None, seg=None, K=None, w=None, want_gw=False,
+                 enc=False):
+    """The one adjoint behind fwi_adjoint{,_ckpt}{,_src} and enc_fwi_adjoint{,_ckpt}: rdq_fwi_adjoint{,_ckpt}{,_src,
+    _enc} over a stored `history`, or (K) over the checkpoint store `ckpt` with every segment recomputed into the
+    scratch `seg`.  `op` names the public op in error messages.  Returns (gA, gk, gbeta, gw); gw is empty unless
+    want_gw."""
     p = _plan(plan)
     _hip.require_device(coeffs, w, history, ckpt, seg, dseis)
-    sz = p.sizes(B)
+    ne = w.shape[1] if enc and w.dim() == 4 else None
+    sz = _sizes(p, B, ne)
     if K is None:
-        if dseis.shape != _seis_shape(p, B) or history.numel() * 4 != sz.history:
+        if dseis.shape != _seis_shape(p, B, ne) or history.numel() * 4 != sz.history:
             raise ValueError(f"{op}: dseis / history do not match the plan")
         stores = [_hip.ptr(history)]
     else:
-        cs = p.ckpt_sizes(B, K)
-        if dseis.shape != _seis_shape(p, B):
+        cs = _ckpt_sizes(p, B, K, ne)
+        if dseis.shape != _seis_shape(p, B, ne):
             raise ValueError(f"{op}: dseis does not match the plan")
         if ckpt.dtype != torch.float32 or seg.dtype != torch.float32 or ckpt.numel() * 4 != cs.ckpt \
                 or seg.numel() * 4 != cs.seg or not ckpt.is_contiguous() or not seg.is_contiguous():
@@ -178,9 +219,11 @@ def _run_adjoint(op, coeffs, dseis, plan, B, history=None, ckpt=None, seg=None, 
                              f"(K = {K}), got {ckpt.numel() * ckpt.element_size()} / {seg.numel() * seg.element_size()}")
         stores = [_hip.ptr(ckpt), _hip.ptr(seg)]
     dseis = dseis.float().contiguous()
-    gw = torch.empty((B, p.ns, p.nt) if want_gw else (0,), dtype=torch.float32, device=coeffs.device)
-    entry = "rdq_fwi_adjoint" + ("_ckpt" if K is not None else "") + ("_src" if w is not None else "")
-    if w is not None:
+    gw = torch.empty(_gw_shape(p, B, ne) if want_gw else (0,), dtype=torch.float32, device=coeffs.device)
+    entry = "rdq_fwi_adjoint" + ("_ckpt" if K is not None else "") + ("_enc" if enc else "_src" if w is not None else "")
+    if enc:
+        w, src = _encoding(p, w, B, gw if want_gw else None)
+    elif w is not None:
         w, src = _source(p, w, B, gw if want_gw else None)
     ring = _f32(sz.ring, coeffs.device)
     gA = _f32(sz.gA, coeffs.device)
@@ -376,12 +419,84 @@ def _(coeffs, w, ckpt, seg, dseis, plan, B, K, want_gw):
     return _fake_adjoint(coeffs, plan, B, want_gw)
 
 
+# ---- encoded supershots (rdq_fwi_*_enc; _encoding above): every per-shot axis holds the ne supershots
+@torch.library.custom_op(f"{LIB}::enc_fwi_forward", mutates_args=())
+def enc_fwi_forward(coeffs: Tensor, weff: Tensor, plan: int, B: int, keep_history: bool) -> Tuple[Tensor, Tensor]:
+    """fwi_forward of ne supershots: wavefield (b, e) takes every source s with the samples weff[b, e, s, n]."""
+    return _run_forward(coeffs, plan, B, keep_history, w=weff, enc=True)
+
+
+@enc_fwi_forward.register_fake
+def _(coeffs, weff, plan, B, keep_history):
+    return _fake_forward(coeffs, plan, B, keep_history, ne=weff.shape[1])
+
+
+@torch.library.custom_op(f"{LIB}::enc_fwi_adjoint", mutates_args=())
+def enc_fwi_adjoint(coeffs: Tensor, weff: Tensor, history: Tensor, dseis: Tensor, plan: int, B: int,
+                    want_gw: bool) -> Tuple[Tensor, Tensor, Tensor, Tensor]:
+    """(gA, gk, gbeta (B * ne * ns), gw): the adjoint of enc_fwi_forward, and gw = d(loss)/d(weff) (B, ne, ns, nt)
+    where want_gw (else empty: the kernel is given no gwav and nothing is allocated)."""
+    return _run_adjoint("enc_fwi_adjoint", coeffs, dseis, plan, B, history=history, w=weff, want_gw=want_gw, enc=True)
+
+
+@enc_fwi_adjoint.register_fake
+def _(coeffs, weff, history, dseis, plan, B, want_gw):
+    return _fake_adjoint(coeffs, plan, B, want_gw, ne=weff.shape[1])
+
+
+@torch.library.custom_op(f"{LIB}::enc_fwi_forward_ckpt", mutates_args=())
+def enc_fwi_forward_ckpt(coeffs: Tensor, weff: Tensor, plan: int, B: int, K: int) -> Tuple[Tensor, Tensor]:
+    """fwi_forward_ckpt of ne supershots."""
+    return _run_forward(coeffs, plan, B, K=K, w=weff, enc=True)
+
+
+@enc_fwi_forward_ckpt.register_fake
+def _(coeffs, weff, plan, B, K):
+    return _fake_forward(coeffs, plan, B, K=K, ne=weff.shape[1])
+
+
+@torch.library.custom_op(f"{LIB}::enc_fwi_adjoint_ckpt", mutates_args=("seg",))
+def enc_fwi_adjoint_ckpt(coeffs: Tensor, weff: Tensor, ckpt: Tensor, seg: Tensor, dseis: Tensor, plan: int, B: int,
+                         K: int, want_gw: bool) -> Tuple[Tensor, Tensor, Tensor, Tensor]:
+    """(gA, gk, gbeta, gw): fwi_adjoint_ckpt of ne supershots (the recompute reads weff again)."""
+    return _run_adjoint("enc_fwi_adjoint_ckpt", coeffs, dseis, plan, B, ckpt=ckpt, seg=seg, K=K, w=weff,
+                        want_gw=want_gw, enc=True)
+
+
+@enc_fwi_adjoint_ckpt.register_fake
+def _(coeffs, weff, ckpt, seg, dseis, plan, B, K, want_gw):
+    return _fake_adjoint(coeffs, plan, B, want_gw, ne=weff.shape[1])
+
+
+@torch.library.custom_op(f"{LIB}::enc_fwi_grad_finalize", mutates_args=())
+def enc_fwi_grad_finalize(coeffs: Tensor, vstat: Tensor, gA: Tensor, gk: Tensor, gbeta: Tensor, plan: int, B: int,
+                          ne: int, vel_mode: int) -> Tensor:
+    """K4 over the accumulators of an encoded adjoint: the ne planes summed in order, gbeta summed over e per source."""
+    p = _plan(plan)
+    _hip.require_device(coeffs, gA)
+    sz = p.sizes_enc(B, ne)
+    if gA.numel() * 4 != sz.gA or gk.numel() * 8 != sz.gk_part or gbeta.numel() * 4 != sz.gbeta:
+        raise ValueError("enc_fwi_grad_finalize: gA / gk / gbeta do not match the plan and ne")
+    colsum = torch.empty(int(sz.colsum) // 8, dtype=torch.float64, device=coeffs.device)
+    out = torch.empty(B, 1, p.nz, p.nx, dtype=torch.float32, device=coeffs.device)
+    _hip.check(p.lib.rdq_fwi_grad_finalize_enc(p.handle, B, ne, _hip.ptr(coeffs), _hip.ptr(vstat), _hip.ptr(gA),
+                                               _hip.ptr(gk), _hip.ptr(gbeta), vel_mode, _hip.ptr(colsum), _hip.ptr(out),
+                                               _hip.stream_of(coeffs)), "rdq_fwi_grad_finalize_enc")
+    return out
+
+
+@enc_fwi_grad_finalize.register_fake
+def _(coeffs, vstat, gA, gk, gbeta, plan, B, ne, vel_mode):
+    p = _plan(plan)
+    return coeffs.new_empty(B, 1, p.nz, p.nx)
+
+
 # ---- the differentiable operators FWIForward calls: K3 + a forward, with the adjoint + K4 as the backward.
 # Outputs (seis, coeffs, vstat, store): only seis is differentiable; coeffs / vstat / the history or checkpoint
 # store are returned for the backward.
-def _fake_fwi(v, plan, keep_history=False, K=None):
+def _fake_fwi(v, plan, keep_history=False, K=None, ne=None):
     coeffs, vstat = _fake_coeffs(v, plan)
-    seis, store = _fake_forward(coeffs, plan, v.shape[0], keep_history, K)
+    seis, store = _fake_forward(coeffs, plan, v.shape[0], keep_history, K, ne)
     return seis, coeffs, vstat, store
 
 
@@ -437,10 +552,38 @@ def _(v, w, plan, vel_mode, K):
     return _fake_fwi(v, plan, K=K)
 
 
-def _register_gradient(op, name, ckpt, src):
-    """The autograd formula of fwi{,_ckpt}{,_src}: inputs (v, [w,] plan, vel_mode, keep_history | K).  The backward
-    is the adjoint op of the same variant (looked up by name when it runs), then K4 for v; w.grad is the adjoint's gw."""
-    adjoint = "fwi_adjoint" + ("_ckpt" if ckpt else "") + ("_src" if src else "")
+@torch.library.custom_op(f"{LIB}::enc_fwi", mutates_args=())
+def enc_fwi(v: Tensor, weff: Tensor, plan: int, vel_mode: int, keep_history: bool) -> Tuple[Tensor, Tensor, Tensor, Tensor]:
+    """seis (B, ne, nrec, ng) = the ne supershots of weff (B, ne, ns, nt) (K3 + the encoded K1); coeffs / vstat /
+    history are for the backward."""
+    coeffs, vstat = fwi_coeffs(v, plan, vel_mode)
+    seis, hist = enc_fwi_forward(coeffs, weff, plan, v.shape[0], keep_history)
+    return seis, coeffs, vstat, hist
+
+
+@enc_fwi.register_fake
+def _(v, weff, plan, vel_mode, keep_history):
+    return _fake_fwi(v, plan, keep_history, ne=weff.shape[1])
+
+
+@torch.library.custom_op(f"{LIB}::enc_fwi_ckpt", mutates_args=())
+def enc_fwi_ckpt(v: Tensor, weff: Tensor, plan: int, vel_mode: int, K: int) -> Tuple[Tensor, Tensor, Tensor, Tensor]:
+    """enc_fwi with the history bounded by recomputation (K steps per segment), as fwi_ckpt."""
+    coeffs, vstat = fwi_coeffs(v, plan, vel_mode)
+    seis, ckpt = enc_fwi_forward_ckpt(coeffs, weff, plan, v.shape[0], K)
+    return seis, coeffs, vstat, ckpt
+
+
+@enc_fwi_ckpt.register_fake
+def _(v, weff, plan, vel_mode, K):
+    return _fake_fwi(v, plan, K=K, ne=weff.shape[1])
+
+
+def _register_gradient(op, name, ckpt, src, enc=False):
+    """The autograd formula of fwi{,_ckpt}{,_src} and enc_fwi{,_ckpt}: inputs (v, [w,] plan, vel_mode, keep_history |
+    K).  The backward is the adjoint op of the same variant (looked up by name when it runs), then K4 for v (enc: the
+    encoded K4); w.grad is the adjoint's gw."""
+    adjoint = ("enc_" if enc else "") + "fwi_adjoint" + ("_ckpt" if ckpt else "") + ("_src" if src and not enc else "")
 
     def setup(ctx, inputs, output):
         v, (plan, vel_mode, last) = inputs[0], inputs[-3:]
@@ -465,12 +608,19 @@ def _register_gradient(op, name, ckpt, src):
         want_v, want_w = ctx.needs_input_grad[0], src and ctx.needs_input_grad[1]
         args = [ctx.coeffs, *ctx.saved_tensors, ctx.store]
         if ckpt:
-            args.append(_f32(_plan(ctx.plan).ckpt_sizes(ctx.B, ctx.K).seg, ctx.coeffs.device))
+            ne = ctx.saved_tensors[0].shape[1] if enc else None
+            args.append(_f32(_ckpt_sizes(_plan(ctx.plan), ctx.B, ctx.K, ne).seg, ctx.coeffs.device))
         args += [gseis.contiguous(), ctx.plan, ctx.B] + ([ctx.K] if ckpt else []) + ([want_w] if src else [])
         gA, gk, gb, *gw = globals()[adjoint](*args)
         ctx.store = None                    # the history / the checkpoint store, and the segment buffer: released as
         del args                            # soon as the adjoint has run
-        g = fwi_grad_finalize(ctx.coeffs, ctx.vstat, gA, gk, gb, ctx.plan, ctx.B, ctx.vel_mode) if want_v else None
+        if not want_v:
+            g = None
+        elif enc:
+            g = enc_fwi_grad_finalize(ctx.coeffs, ctx.vstat, gA, gk, gb, ctx.plan, ctx.B, ctx.saved_tensors[0].shape[1],
+                                      ctx.vel_mode)
+        else:
+            g = fwi_grad_finalize(ctx.coeffs, ctx.vstat, gA, gk, gb, ctx.plan, ctx.B, ctx.vel_mode)
         return (g, gw[0] if want_w else None, None, None, None) if src else (g, None, None, None)
 
     op.register_autograd(backward, setup_context=setup)
@@ -480,6 +630,8 @@ _register_gradient(fwi, "fwi", ckpt=False, src=False)
 _register_gradient(fwi_ckpt, "fwi_ckpt", ckpt=True, src=False)
 _register_gradient(fwi_src, "fwi_src", ckpt=False, src=True)
 _register_gradient(fwi_ckpt_src, "fwi_ckpt_src", ckpt=True, src=True)
+_register_gradient(enc_fwi, "enc_fwi", ckpt=False, src=True, enc=True)
+_register_gradient(enc_fwi_ckpt, "enc_fwi_ckpt", ckpt=True, src=True, enc=True)
 
 
 # ---------------------------------------------------------------------------------------- U-Net

@@ -85,6 +85,26 @@ class FwiPlan:
             self._sizes[B] = s
         return self._sizes[B]
 
+    def sizes_enc(self, B, ne):
+        """rdq_fwi_sizes_t of an encoded call with ne supershots per model (rdq_fwi_sizes_enc): the buffers of
+        sizes(B) with ns replaced by ne, and gbeta (B, ne, ns)."""
+        key = ("enc", int(B), int(ne))
+        if key not in self._sizes:
+            s = _hip.FwiSizes()
+            _hip.check(self.lib.rdq_fwi_sizes_enc(self.handle, int(B), int(ne), ctypes.byref(s)), "rdq_fwi_sizes_enc")
+            self._sizes[key] = s
+        return self._sizes[key]
+
+    def ckpt_sizes_enc(self, B, ne, K):
+        """ckpt_sizes for an encoded call with ne supershots per model."""
+        key = ("ckpt_enc", int(B), int(ne), int(K))
+        if key not in self._sizes:
+            s = _hip.FwiCkptSizes()
+            _hip.check(self.lib.rdq_fwi_ckpt_sizes_enc(self.handle, int(B), int(ne), int(K), ctypes.byref(s)),
+                       "rdq_fwi_ckpt_sizes_enc")
+            self._sizes[key] = s
+        return self._sizes[key]
+
     def set_graphs(self, enable):
         _hip.check(self.lib.rdq_fwi_set_graphs(self.handle, int(bool(enable))), "rdq_fwi_set_graphs")
 
@@ -515,7 +535,63 @@ class FWIForward(nn.Module):
             w = w[..., self.shots[0]:self.shots[1], :]
         return w.expand(B, self.shots[1] - self.shots[0], nt)
 
-    def forward(self, v, wavelet=None):
+    def _call_encoding(self, v, E):
+        """Checks an encoding against v and the survey (before any device work) and returns it as (B, ne, ns) fp32:
+        a shared model axis is an expand(), so autograd sums its gradient."""
+        if self.shots_explicit:
+            raise ValueError("encoding= fires every source of the survey into each supershot: it is not available on "
+                             "an instance constructed with shots=")
+        if not isinstance(E, torch.Tensor) or not E.is_floating_point():
+            raise ValueError("encoding must be a float tensor of shape (ne, ns) or (B, ne, ns)")
+        if v.dim() != 4 or v.shape[1] != 1:
+            raise ValueError(f"expected v of shape (B,1,H,W), got {tuple(v.shape)}")
+        B, ns = v.shape[0], len(self.ctx["sx"])
+        if E.dim() not in (2, 3) or E.shape[-1] != ns or (E.dim() == 3 and E.shape[0] != B):
+            raise ValueError(f"encoding must have shape (ne, {ns}) or ({B}, ne, {ns}) (supershots, sources; models, "
+                             f"supershots, sources), got {tuple(E.shape)}")
+        if E.shape[-2] < 1:
+            raise ValueError("encoding needs at least one supershot (ne >= 1)")
+        if E.device != v.device:
+            raise ValueError(f"encoding is on {E.device}, v on {v.device}")
+        if E.dtype != torch.float32:
+            E = E.float()
+        return E.expand(B, E.shape[-2], ns)
+
+    def _encoded(self, v, wavelet, E):
+        """forward(v, wavelet, encoding=E): see forward."""
+        E = self._call_encoding(v, E)                      # ValueErrors before any device work
+        if wavelet is not None:
+            w = self._call_wavelet(v, wavelet)
+        _hip.require_device(v)
+        if v.dtype != torch.float32:
+            v = v.float()
+        if self._fused_denorm():
+            vel_mode = 0
+        else:
+            if self.normalize:
+                v = self.v_denorm_func(v)
+            vel_mode = 1
+        plan = self._plan(v.shape[2], v.shape[3], v.device, per_call=wavelet is not None)
+        self._last = plan
+        B, ne = E.shape[0], E.shape[1]
+        if wavelet is None:      # the constructor's (or the Ricker) signature, as the plan holds it: fp32 of the fp64
+            w = torch.from_numpy(plan._wav).to(device=v.device, dtype=torch.float32).expand(B, plan.ns, plan.nt)
+        weff = E.unsqueeze(-1) * w.unsqueeze(1)            # (B, ne, ns, nt): autograd gives E.grad and w.grad from gwav
+        keep = bool((v.requires_grad or weff.requires_grad) and torch.is_grad_enabled())
+        K = None
+        if keep:
+            if isinstance(self.checkpoint, int):
+                K = self.checkpoint
+            elif self.history_budget_gb is not None:
+                K = choose_checkpoint(plan.nt, plan.sizes_enc(B, ne).history // (plan.nt + 2),
+                                      int(float(self.history_budget_gb) * 2 ** 30))
+        if K is not None:
+            s = torch.ops.red_diffeq.enc_fwi_ckpt(v, weff, plan.op_id, vel_mode, K)[0]
+        else:
+            s = torch.ops.red_diffeq.enc_fwi(v, weff, plan.op_id, vel_mode, keep)[0]
+        return self.s_norm_func(s) if self.normalize else s
+
+    def forward(self, v, wavelet=None, encoding=None):
         """seis = forward(v).  wavelet: None = the constructor's wavelet (the Ricker by default) on the plan's
         kernels, today's path.  Otherwise a float tensor on v's device of shape (nt,), (ns, nt) or (B, ns, nt)
         (ns = the survey's full shot count, also with shots=): sample n of model b, shot s is injected as
@@ -523,8 +599,25 @@ class FWIForward(nn.Module):
         (a shared wavelet receives the fp32 sum of the per-shot gradients).  Such a call always runs the narrow
         chunked kernels (set_tuning's depths and chains), store-all or checkpointed as the instance says.  By
         linearity J_w dw is forward(v, wavelet=dw) under no_grad.  born / gauss_newton take no wavelet: they use
-        the constructor's.  Not covered: per-call wavelets on the persistent or wide kernels, several source
-        points per shot, engine / YAML wiring of per-shot wavelets."""
+        the constructor's.
+
+        encoding: None, or a float tensor E on v's device of shape (ne, ns) or (B, ne, ns): source encoding.  The
+        call models ne simultaneous-source "supershots" per model instead of ns shots: wavefield (b, e) is fired by
+        every source s at once with the effective wavelet E[b, e, s] * w[b, s, :] (w = wavelet=, or the
+        constructor's / Ricker signature; the product is formed with torch ops), the sources injected in ascending
+        s, each one including those whose code is zero.  Returns (B, ne, nrec, ng), through s_norm_func like the
+        plain call, differentiable in v, E and the wavelet (broadcast axes receive the fp32 sums).  It runs the
+        narrow chunked kernels, store-all or checkpointed as the instance says; time and history scale with ne, not
+        ns.  A row of E with a single 1 reproduces forward(v, wavelet=w)[:, s] bit for bit.  Codes and the matching
+        combination of observed data: red_diffeq.utils.encoding (random_encoding, encode).  ValueError for a wrong
+        shape, dtype or device, ne < 1, or an instance constructed with shots=.
+
+        Not covered: per-call wavelets or encodings on the persistent or wide kernels; born / gauss_newton with an
+        encoding (they take none); shots= sharding of a supershot; engine / YAML wiring of per-shot wavelets or of
+        encodings (redraw schedules, encoded observed data inside InversionEngine: the two helpers are what a caller
+        needs to do it by hand)."""
+        if encoding is not None:
+            return self._encoded(v, wavelet, encoding)
         if wavelet is not None:
             wavelet = self._call_wavelet(v, wavelet)      # ValueError before any device work
         _hip.require_device(v)
@@ -606,7 +699,13 @@ class FWIForward(nn.Module):
     def _custom_s_norm(self):
         return self.normalize and self.s_norm_func is not s_normalize_none
 
-    def born(self, v, dv, return_seis=False, history=True):
+    @staticmethod
+    def _no_encoding(what, encoding):
+        if encoding is not None:
+            raise ValueError(f"{what} takes no encoding=: it linearises the per-shot survey (encoded supershots are "
+                             f"forward(v, encoding=E) only)")
+
+    def born(self, v, dv, return_seis=False, history=True, encoding=None):
         """Linearised (Born) modelling: J dv, J = d forward(v) / d v, with the shape of forward(v); with
         return_seis, (forward(v), J dv).  Runs under no_grad; the result does not require grad.  history=True
         (the default): the forward keeps its store-all history and the Born pass streams it back (ValueError with
@@ -614,7 +713,9 @@ class FWIForward(nn.Module):
         computes the forward and its tangent together and keeps no history at all (no budget applies); both
         outputs are bit-identical to history=True's.  A custom v_denorm_func, and an s_norm_func other than
         s_normalize_none, are chained with torch.func.jvp.  With shots=, this rank's shots only, as forward.  The source is
-        the constructor's wavelet (born and gauss_newton take no wavelet= of their own)."""
+        the constructor's wavelet (born and gauss_newton take no wavelet= of their own, and no encoding=: passing one
+        raises ValueError)."""
+        self._no_encoding("born", encoding)
         v, dv, vel_mode, _ = self._linearise(v, dv, "born")
         with torch.no_grad():
             if history:
@@ -626,13 +727,14 @@ class FWIForward(nn.Module):
         seis, ds = seis.detach(), ds.detach()
         return (seis, ds) if return_seis else ds
 
-    def gauss_newton(self, v, dv, weight=None, history=True):
+    def gauss_newton(self, v, dv, weight=None, history=True, encoding=None):
         """The Gauss-Newton product J^T (weight * J dv), with the shape of v.  history=True (the default): one
         forward with history, one Born pass, then the adjoint and the finalize on the same history (no second
         forward).  Bit-equal to s = forward(v); s.backward(weight * born(v, dv)); v.grad.  history=False: the
         fused forward + Born pass, which also writes the checkpoint store of checkpoint_interval(), then the
         checkpointed adjoint and the finalize: the memory of a checkpointed gradient, bit-equal to the same
         three lines on this instance.  It needs checkpoint= or history_budget_gb (ValueError otherwise)."""
+        self._no_encoding("gauss_newton", encoding)
         v, dv, vel_mode, pull = self._linearise(v, dv, "gauss_newton", need_checkpoint=not history)
         with torch.no_grad():
             if history:

@@ -3,7 +3,13 @@
 commits).  A function body is the text from its label to its .Lfunc_end label, comments and blank lines
 stripped; the bodies are compared as text, symbol by symbol, and nothing else is looked at.
 
-    kernel_text_diff.py OLD.s NEW.s [--show REGEX]
+    kernel_text_diff.py OLD.s NEW.s [--show REGEX] [--normalize] [--rename REGEX=REPL ...]
+
+--normalize makes the comparison independent of where a function stands in the file and of its own symbol: the
+function index in local labels (.LBB12_3 -> .LBB_3, likewise .LJTI / .Ltmp) and the function's own mangled name are
+replaced by placeholders.  It is needed whenever functions are added or removed, which renumbers every later one.
+--rename rewrites the demangled names of OLD before pairing (re.sub), for a kernel whose template parameters
+changed spelling but not meaning, e.g. --rename 'k_adj_tb<(\d), false>=k_adj_tb<\1, 0>'.
 
 prints `identical N, differing M, only in one file K`, the differing symbols, and with --show the unified diff
 of the differing symbols whose (demangled) name matches.  Exit status 1 if anything differs."""
@@ -14,10 +20,12 @@ import subprocess
 import sys
 
 
-def bodies(path):
+def bodies(path, normalize=False):
     out, name, body = {}, None, []
     for line in open(path):
         line = line.split(";", 1)[0].rstrip()
+        if normalize and name is not None:
+            line = re.sub(r"\.(LBB|LJTI|Ltmp)\d+_", r".\1_", line.replace(name, "@self"))
         if not line.strip():
             continue
         if name is None:
@@ -46,9 +54,21 @@ def main():
     ap.add_argument("old")
     ap.add_argument("new")
     ap.add_argument("--show", default=None, help="print the diff of differing symbols matching this regex")
+    ap.add_argument("--normalize", action="store_true", help="ignore function numbering in local labels and own name")
+    ap.add_argument("--rename", action="append", default=[], metavar="REGEX=REPL",
+                    help="rewrite OLD's demangled names before pairing (implies pairing by demangled name)")
     args = ap.parse_args()
-    a, b = bodies(args.old), bodies(args.new)
+    a, b = bodies(args.old, args.normalize), bodies(args.new, args.normalize)
     pretty = demangle(sorted(set(a) | set(b)))
+    if args.rename:      # pair by demangled name, OLD's rewritten
+        def renamed(n):
+            for r in args.rename:
+                pat, repl = r.split("=", 1)
+                n = re.sub(pat, repl, n)
+            return n
+        a = {renamed(pretty[n]): v for n, v in a.items()}
+        b = {pretty[n]: v for n, v in b.items()}
+        pretty = {n: n for n in set(a) | set(b)}
     same = [n for n in a if n in b and a[n] == b[n]]
     diff = [n for n in a if n in b and a[n] != b[n]]
     only = sorted(set(a) ^ set(b))
