@@ -222,6 +222,11 @@ __global__ __launch_bounds__(256) void k_conv_reduce(int S, int64_t total, int N
 // per tile, then the slabs summed in slab order, then bias and residual: the arithmetic of
 // k_conv_reduce, bit for bit) instead of a separate launch.  Tickets are zero before the launch and
 // returned to zero by the combining workgroup.
+// the reference's exact activations, written once: nn.SiLU as v / (1 + exp(-v)) with expf and a true division
+// (gn_silu1, k_linear, wave_dot, lsm_rows, k_linear_silu_multi_b, k_wdot_silu_b); nn.GELU (erf form) as
+// (0.5 v) (1 + erf(v / sqrt 2)) in that association (k_linear, time_mlp_rows; k_time_mlp_b restates it)
+__device__ __forceinline__ float silu_exact(float v) { return v / (1.0f + expf(-v)); }
+__device__ __forceinline__ float gelu_exact(float v) { return 0.5f * v * (1.0f + erff(v * 0.70710678118654752f)); }
 // GroupNorm-normalised value -> affine -> time scale/shift -> SiLU (Block.forward, diffusion.py:142-149)
 __device__ __forceinline__ float gn_silu1(float x, float mean, float rstd, float ga, float be, bool sso, float sc1,
                                           float sh)
@@ -229,7 +234,7 @@ __device__ __forceinline__ float gn_silu1(float x, float mean, float rstd, float
     float v = (x - mean) * rstd;
     v = v * ga + be;
     if (sso) v = v * sc1 + sh;
-    return v / (1.0f + expf(-v));
+    return silu_exact(v);
 }
 
 // element loads of a normalise pass's input: fp32, or the bf16 halo-staged conv's raw output
@@ -777,17 +782,67 @@ __global__ __launch_bounds__(256) void k_gn_partial(const float *__restrict__ x,
     if (threadIdx.x == 0) { part[((size_t)bg * nchunk + c) * 2] = ss[0]; part[((size_t)bg * nchunk + c) * 2 + 1] = sq[0]; }
 }
 
+// {mean, 1/std} of a group of n elements from its fp64 sum s and sum of squares q: mean = s / n,
+// var = max(q / n - mean mean, 0), 1 / sqrt(var + eps), all in fp64 and rounded to fp32 last.  Every GroupNorm
+// form ends here: gn_stat_of (chunk partials), gn_tile_stats and k_gn_apply_out (conv tile partials).
+// (Returned, not written through references: with reference outputs k_gn_stats' text changes.)
+__device__ __forceinline__ float2 gn_finish(double s, double q, double n, float eps)
+{
+    const double mean = s / n;
+    double var = q / n - mean * mean;
+    var = var < 0.0 ? 0.0 : var;
+    return float2{(float)mean, (float)(1.0 / sqrt(var + (double)eps))};
+}
+// mean and 1/std of (sample b, group g) from the producing conv's per-tile partials gnp[m tile][G][slot][s, q]
+// (tiles of bm flattened pixels; slot 0 / 1: the first / second sample a tile spans).  Called by one whole wave:
+// lane l adds tiles mlo + l, mlo + l + 64, ... of the sample in that order, then a fixed xor tree (32, 16, ..,
+// 1) in fp64; lane 0 finishes (gn_finish) and writes the two floats.  This order is what makes every normalise
+// pass on conv statistics agree bit for bit: wave 0 of k_gn_apply_t and k_gn_apply8 call it, k_gn_apply_out
+// restates it per group (there the call changes the kernel's text).  gnp without __restrict__: with it the
+// text of k_gn_apply8 changes.
+__device__ __forceinline__ void gn_tile_stats(int b, int g, int cpg, int HW, int G, int bm, const double *gnp,
+                                              float eps, int lane, float &mean_f, float &rstd_f)
+{
+    const int mlo = (int)(((int64_t)b * HW) / bm), mhi = (int)(((int64_t)(b + 1) * HW - 1) / bm);
+    double s = 0.0, q = 0.0;
+    for (int mt = mlo + lane; mt <= mhi; mt += 64) {
+        const int slot = (int)(((int64_t)mt * bm) / HW) == b ? 0 : 1;
+        const double *p = gnp + (((size_t)mt * G + g) * 2 + slot) * 2;
+        s += p[0];
+        q += p[1];
+    }
+#pragma unroll
+    for (int o = 32; o > 0; o >>= 1) {
+        s += __shfl_xor(s, o, 64);
+        q += __shfl_xor(q, o, 64);
+    }
+    if (lane == 0) {
+        const float2 r = gn_finish(s, q, (double)cpg * HW, eps);
+        mean_f = r.x;
+        rstd_f = r.y;
+    }
+}
+// the time conditioning of channel c of sample b from ss[B][2 C] (scale | shift), as gn_silu1 takes it: scale + 1
+// (the `+ 1` is done once, here) and shift; sso = ss != nullptr, the caller's own flag (0 without conditioning).
+// Every normalise pass: k_gn_apply, k_gn_apply_t's SMALL loop, k_gn_apply8, k_gn_apply_out; k_gn_apply_t's
+// per-channel pair restates them (the calls there invert a branch of the <false, ..> instantiations).
+__device__ __forceinline__ float gn_scale1(bool sso, const float *ss, int b, int C, int c)
+{
+    return sso ? ss[(size_t)b * 2 * C + c] + 1.0f : 0.0f;
+}
+__device__ __forceinline__ float gn_shift(bool sso, const float *ss, int b, int C, int c)
+{
+    return sso ? ss[(size_t)b * 2 * C + C + c] : 0.0f;
+}
 // mean and 1/std of (sample, group) bg from the fixed-order fp64 chunk partials
 __device__ __forceinline__ void gn_stat_of(int bg, int nchunk, int64_t gsize, float eps, const double *part,
                                            float &mean_f, float &rstd_f)
 {
     double s = 0.0, q = 0.0;
     for (int c = 0; c < nchunk; ++c) { s += part[((size_t)bg * nchunk + c) * 2]; q += part[((size_t)bg * nchunk + c) * 2 + 1]; }
-    const double mean = s / (double)gsize;
-    double var = q / (double)gsize - mean * mean;
-    var = var < 0.0 ? 0.0 : var;
-    mean_f = (float)mean;
-    rstd_f = (float)(1.0 / sqrt(var + (double)eps));
+    const float2 r = gn_finish(s, q, (double)gsize, eps);
+    mean_f = r.x;
+    rstd_f = r.y;
 }
 // ... once per (sample, group), for large grids (the apply's workgroups then read two floats)
 __global__ __launch_bounds__(256) void k_gn_stats(int BG, int nchunk, int64_t gsize, float eps,
@@ -830,13 +885,13 @@ __global__ __launch_bounds__(256) void k_gn_apply(int C, int HW, int G, int nch,
         const size_t base = ((size_t)b * C + g * cpg + cl0) * HW;
         for (int e = threadIdx.x; e < n; e += 256) {
             const int cc = g * cpg + cl0 + e / HW;
-            const float s1 = sso ? ss[(size_t)b * 2 * C + cc] + 1.0f : 0.0f, sh1 = sso ? ss[(size_t)b * 2 * C + C + cc] : 0.0f;
+            const float s1 = gn_scale1(sso, ss, b, C, cc), sh1 = gn_shift(sso, ss, b, C, cc);
             y[base + e] = gn_silu1(x[base + e], mean, rstd, gamma[cc], beta[cc], sso, s1, sh1);
         }
         return;
     }
     const float ga = gamma[c], be = beta[c];
-    const float sc1 = sso ? ss[(size_t)b * 2 * C + c] + 1.0f : 0.0f, sh = sso ? ss[(size_t)b * 2 * C + C + c] : 0.0f;
+    const float sc1 = gn_scale1(sso, ss, b, C, c), sh = gn_shift(sso, ss, b, C, c);
     const float *px = x + ((size_t)b * C + c) * HW;
     float *py = y + ((size_t)b * C + c) * HW;
     if ((HW & 3) == 0) {
@@ -857,7 +912,7 @@ __global__ __launch_bounds__(256) void k_gn_apply(int C, int HW, int G, int nch,
 
 // the same pass on statistics accumulated by the producing conv (k_conv_cc, a.gnp): wave 0 of each
 // workgroup sums its (sample, group)'s per-tile partials — lane l takes tiles l, l+64, ... of the
-// sample in order, then a fixed xor tree — and the pass adds an optional residual after the SiLU
+// sample in order, then a fixed xor tree (gn_tile_stats) — and the pass adds an optional residual after the SiLU
 // (ResnetBlock's identity shortcut, diffusion.py:168).  V float4 per thread (large batches: V = 4, so
 // the per-workgroup statistics reduction is paid once per 4096 elements instead of 1024)
 template <bool SMALL, int V = 1, typename TX = float>
@@ -886,31 +941,10 @@ __global__ __launch_bounds__(256) void k_gn_apply_t(int C, int HW, int G, int nc
     }
     const float ga = gamma[c], be = beta[c];
     const bool sso = ss != nullptr;
+    // gn_scale1 / gn_shift, written out (see there)
     const float sc1 = sso ? ss[(size_t)b * 2 * C + c] + 1.0f : 0.0f, sh = sso ? ss[(size_t)b * 2 * C + C + c] : 0.0f;
     __shared__ float st2[2];
-    if (threadIdx.x < 64) {
-        const int lane = threadIdx.x;
-        const int mlo = (int)(((int64_t)b * HW) / bm), mhi = (int)(((int64_t)(b + 1) * HW - 1) / bm);
-        double s = 0.0, q = 0.0;
-        for (int mt = mlo + lane; mt <= mhi; mt += 64) {
-            const int slot = (int)(((int64_t)mt * bm) / HW) == b ? 0 : 1;
-            const double *p = gnp + (((size_t)mt * G + g) * 2 + slot) * 2;
-            s += p[0];
-            q += p[1];
-        }
-#pragma unroll
-        for (int o = 32; o > 0; o >>= 1) {
-            s += __shfl_xor(s, o, 64);
-            q += __shfl_xor(q, o, 64);
-        }
-        if (lane == 0) {
-            const double n = (double)cpg * HW, mean = s / n;
-            double var = q / n - mean * mean;
-            var = var < 0.0 ? 0.0 : var;
-            st2[0] = (float)mean;
-            st2[1] = (float)(1.0 / sqrt(var + (double)eps));
-        }
-    }
+    if (threadIdx.x < 64) gn_tile_stats(b, g, cpg, HW, G, bm, gnp, eps, threadIdx.x, st2[0], st2[1]);
     __syncthreads();
     const float mean = st2[0], rstd = st2[1];
     if constexpr (SMALL) {        // small images: -nch whole channels of the group per workgroup
@@ -918,7 +952,7 @@ __global__ __launch_bounds__(256) void k_gn_apply_t(int C, int HW, int G, int nc
         const size_t base0 = ((size_t)b * C + g * cpg + cl0) * HW;
         for (int e = threadIdx.x; e < n; e += 256) {
             const int cc = g * cpg + cl0 + e / HW;
-            const float s1 = sso ? ss[(size_t)b * 2 * C + cc] + 1.0f : 0.0f, sh1 = sso ? ss[(size_t)b * 2 * C + C + cc] : 0.0f;
+            const float s1 = gn_scale1(sso, ss, b, C, cc), sh1 = gn_shift(sso, ss, b, C, cc);
             float u = gn_silu1(ldx(x + base0 + e), mean, rstd, gamma[cc], beta[cc], sso, s1, sh1);
             if (post) u += post[base0 + e];
             y[base0 + e] = u;
@@ -949,138 +983,71 @@ __global__ __launch_bounds__(256) void k_gn_apply_t(int C, int HW, int G, int nc
     }
 }
 
+// k_gn_apply8's P adjacent pixels of one channel: a float (ldx), or for P = 2 a float2 from one 4-byte load
+// of two bf16 pixels (ldx2); pix_of<U> is pixel U of either.  (The pixels stay a float / a float2 and the two
+// pixels are written out in the kernel: as float[P] arrays under loops over P the P = 2 text changes.)
+__device__ __forceinline__ float2 ldx2(const __bf16 *p)
+{
+    const unsigned u = *reinterpret_cast<const unsigned *>(p);
+    return float2{__uint_as_float(u << 16), __uint_as_float(u & 0xffff0000u)};
+}
+template <int P, typename TX>
+__device__ __forceinline__ auto ldxp(const TX *p)
+{
+    if constexpr (P == 2) return ldx2(p);
+    else return ldx(p);
+}
+template <int U> __device__ __forceinline__ float pix_of(float v) { return v; }
+template <int U> __device__ __forceinline__ float pix_of(const float2 &v) { return U ? v.y : v.x; }
+
 // k_gn_apply_t's pass for a Block whose output feeds ONLY the next 3x3 bf16 conv (ResnetBlock's block1,
 // diffusion.py:166-167): the same per-element arithmetic (statistics from the conv's per-tile
 // partials, GN -> scale / shift -> SiLU), rounded to bf16 and stored as channel octets
 // [B][C / 8][HW][8], the layout k_conv3_bf16<.., IN8> gathers with one 16-byte load per pixel.  The
 // consumer rounds its operands to bf16 anyway, so its result is bit-identical to the fp32 path's
-// while this pass writes half the bytes and the conv reads half.  Workgroup: 256 pixels of one
+// while this pass writes half the bytes and the conv reads half.  Workgroup: 256 P pixels of one
 // (sample, group), every octet of the group.
-template <typename TX = float>
+// P = 2 (the bf16 conv output, even HW, so p + 1 < HW whenever p < HW): two adjacent pixels per thread, one
+// 4-byte load per channel and 32 contiguous output bytes per thread instead of 2-byte loads and one 16-byte
+// store; the same template, so per element the arithmetic and the octets are P = 1's.
+template <int P = 1, typename TX = float>
 __global__ __launch_bounds__(256) void k_gn_apply8(int C, int HW, int G, const TX *__restrict__ x,
                                                    const float *__restrict__ gamma, const float *__restrict__ beta,
                                                    const float *__restrict__ ss, const double *__restrict__ gnp,
                                                    float eps, __bf16 *__restrict__ y, int bm)
 {
     const int bg = blockIdx.y, b = bg / G, g = bg - b * G, cpg = C / G;
-    const int p = blockIdx.x * 256 + (int)threadIdx.x;
+    const int p = (blockIdx.x * 256 + (int)threadIdx.x) * P;
     __shared__ float st2[2];
-    if (threadIdx.x < 64) {                     // (sample, group) statistics: k_gn_apply_t's reduction
-        const int lane = threadIdx.x;
-        const int mlo = (int)(((int64_t)b * HW) / bm), mhi = (int)(((int64_t)(b + 1) * HW - 1) / bm);
-        double s = 0.0, q = 0.0;
-        for (int mt = mlo + lane; mt <= mhi; mt += 64) {
-            const int slot = (int)(((int64_t)mt * bm) / HW) == b ? 0 : 1;
-            const double *pp = gnp + (((size_t)mt * G + g) * 2 + slot) * 2;
-            s += pp[0];
-            q += pp[1];
-        }
-#pragma unroll
-        for (int o = 32; o > 0; o >>= 1) {
-            s += __shfl_xor(s, o, 64);
-            q += __shfl_xor(q, o, 64);
-        }
-        if (lane == 0) {
-            const double n = (double)cpg * HW, mean = s / n;
-            double var = q / n - mean * mean;
-            var = var < 0.0 ? 0.0 : var;
-            st2[0] = (float)mean;
-            st2[1] = (float)(1.0 / sqrt(var + (double)eps));
-        }
-    }
+    if (threadIdx.x < 64) gn_tile_stats(b, g, cpg, HW, G, bm, gnp, eps, threadIdx.x, st2[0], st2[1]);
     // this thread's first octet in flight behind the statistics
-    const int pc = min(p, HW - 1);
+    const int pc = min(p, HW - P);
     const TX *xb = x + ((size_t)b * C + g * cpg) * HW + pc;
-    float v[8];
+    using XP = decltype(ldxp<P>(x));
+    XP v[8];
 #pragma unroll
-    for (int j = 0; j < 8; ++j) v[j] = ldx(xb + (size_t)j * HW);
+    for (int j = 0; j < 8; ++j) v[j] = ldxp<P>(xb + (size_t)j * HW);
     __syncthreads();
     const float mean = st2[0], rstd = st2[1];
     const bool sso = ss != nullptr;
     for (int o = 0; o < cpg / 8; ++o) {
-        float nx[8];
+        XP nx[8];
         if (o + 1 < cpg / 8) {
 #pragma unroll
-            for (int j = 0; j < 8; ++j) nx[j] = ldx(xb + (size_t)(8 * (o + 1) + j) * HW);
+            for (int j = 0; j < 8; ++j) nx[j] = ldxp<P>(xb + (size_t)(8 * (o + 1) + j) * HW);
         }
-        bf16x8 h;
+        bf16x8 h[P];
 #pragma unroll
         for (int j = 0; j < 8; ++j) {
             const int c = g * cpg + 8 * o + j;
-            const float sc1 = sso ? ss[(size_t)b * 2 * C + c] + 1.0f : 0.0f, sh = sso ? ss[(size_t)b * 2 * C + C + c] : 0.0f;
-            h[j] = (__bf16)gn_silu1(v[j], mean, rstd, gamma[c], beta[c], sso, sc1, sh);
-        }
-        if (p < HW) *reinterpret_cast<bf16x8 *>(y + (((size_t)b * (C >> 3) + (g * cpg >> 3) + o) * HW + p) * 8) = h;
-#pragma unroll
-        for (int j = 0; j < 8; ++j) v[j] = nx[j];
-    }
-}
-
-// k_gn_apply8 on the bf16 conv output with two adjacent pixels per thread (even HW): one 4-byte load per
-// channel and 32 contiguous output bytes per thread instead of 2-byte loads and one 16-byte store;
-// per element the same arithmetic, so the octets are k_gn_apply8's bit for bit.
-__device__ __forceinline__ float2 ldx2(const __bf16 *p)
-{
-    const unsigned u = *reinterpret_cast<const unsigned *>(p);
-    return float2{__uint_as_float(u << 16), __uint_as_float(u & 0xffff0000u)};
-}
-__global__ __launch_bounds__(256) void k_gn_apply8x2(int C, int HW, int G, const __bf16 *__restrict__ x,
-                                                     const float *__restrict__ gamma, const float *__restrict__ beta,
-                                                     const float *__restrict__ ss, const double *__restrict__ gnp,
-                                                     float eps, __bf16 *__restrict__ y, int bm)
-{
-    const int bg = blockIdx.y, b = bg / G, g = bg - b * G, cpg = C / G;
-    const int p = (blockIdx.x * 256 + (int)threadIdx.x) * 2;   // HW even: p + 1 < HW whenever p < HW
-    __shared__ float st2[2];
-    if (threadIdx.x < 64) {                     // (sample, group) statistics: k_gn_apply_t's reduction
-        const int lane = threadIdx.x;
-        const int mlo = (int)(((int64_t)b * HW) / bm), mhi = (int)(((int64_t)(b + 1) * HW - 1) / bm);
-        double s = 0.0, q = 0.0;
-        for (int mt = mlo + lane; mt <= mhi; mt += 64) {
-            const int slot = (int)(((int64_t)mt * bm) / HW) == b ? 0 : 1;
-            const double *pp = gnp + (((size_t)mt * G + g) * 2 + slot) * 2;
-            s += pp[0];
-            q += pp[1];
-        }
-#pragma unroll
-        for (int o = 32; o > 0; o >>= 1) {
-            s += __shfl_xor(s, o, 64);
-            q += __shfl_xor(q, o, 64);
-        }
-        if (lane == 0) {
-            const double n = (double)cpg * HW, mean = s / n;
-            double var = q / n - mean * mean;
-            var = var < 0.0 ? 0.0 : var;
-            st2[0] = (float)mean;
-            st2[1] = (float)(1.0 / sqrt(var + (double)eps));
-        }
-    }
-    const int pc = min(p, HW - 2);
-    const __bf16 *xb = x + ((size_t)b * C + g * cpg) * HW + pc;
-    float2 v[8];
-#pragma unroll
-    for (int j = 0; j < 8; ++j) v[j] = ldx2(xb + (size_t)j * HW);
-    __syncthreads();
-    const float mean = st2[0], rstd = st2[1];
-    const bool sso = ss != nullptr;
-    for (int o = 0; o < cpg / 8; ++o) {
-        float2 nx[8];
-        if (o + 1 < cpg / 8) {
-#pragma unroll
-            for (int j = 0; j < 8; ++j) nx[j] = ldx2(xb + (size_t)(8 * (o + 1) + j) * HW);
-        }
-        bf16x8 h0, h1;
-#pragma unroll
-        for (int j = 0; j < 8; ++j) {
-            const int c = g * cpg + 8 * o + j;
-            const float sc1 = sso ? ss[(size_t)b * 2 * C + c] + 1.0f : 0.0f, sh = sso ? ss[(size_t)b * 2 * C + C + c] : 0.0f;
-            h0[j] = (__bf16)gn_silu1(v[j].x, mean, rstd, gamma[c], beta[c], sso, sc1, sh);
-            h1[j] = (__bf16)gn_silu1(v[j].y, mean, rstd, gamma[c], beta[c], sso, sc1, sh);
+            const float sc1 = gn_scale1(sso, ss, b, C, c), sh = gn_shift(sso, ss, b, C, c);
+            h[0][j] = (__bf16)gn_silu1(pix_of<0>(v[j]), mean, rstd, gamma[c], beta[c], sso, sc1, sh);
+            if constexpr (P == 2) h[1][j] = (__bf16)gn_silu1(pix_of<1>(v[j]), mean, rstd, gamma[c], beta[c], sso, sc1, sh);
         }
         if (p < HW) {
             bf16x8 *yo = reinterpret_cast<bf16x8 *>(y + (((size_t)b * (C >> 3) + (g * cpg >> 3) + o) * HW + p) * 8);
-            yo[0] = h0;
-            yo[1] = h1;
+            yo[0] = h[0];
+            if constexpr (P == 2) yo[1] = h[1];
         }
 #pragma unroll
         for (int j = 0; j < 8; ++j) v[j] = nx[j];
@@ -1120,7 +1087,8 @@ __global__ __launch_bounds__(64 * GO_NW) void k_gn_apply_out(int C, int HW, int 
         xv[u] = ldx(x + o);
         rv[u] = post ? post[o] : 0.0f;
     }
-    // (sample, group) statistics: wave w reduces groups w, w + GO_NW, ... exactly as k_gn_apply_t's wave 0
+    // (sample, group) statistics: wave w reduces groups w, w + GO_NW, ...; the loop body is gn_tile_stats written
+    // out (a call here reorders this kernel's loop preamble), and must stay its twin line for line
     for (int g = wv; g < G; g += GO_NW) {
         const int mlo = (int)(((int64_t)b * HW) / bm), mhi = (int)(((int64_t)(b + 1) * HW - 1) / bm);
         double s = 0.0, q = 0.0;
@@ -1136,11 +1104,9 @@ __global__ __launch_bounds__(64 * GO_NW) void k_gn_apply_out(int C, int HW, int 
             q += __shfl_xor(q, o, 64);
         }
         if (lane == 0) {
-            const double n = (double)cpg * HW, mean = s / n;
-            double var = q / n - mean * mean;
-            var = var < 0.0 ? 0.0 : var;
-            st[g][0] = (float)mean;
-            st[g][1] = (float)(1.0 / sqrt(var + (double)eps));
+            const float2 r = gn_finish(s, q, (double)cpg * HW, eps);
+            st[g][0] = r.x;
+            st[g][1] = r.y;
         }
     }
     __syncthreads();
@@ -1150,7 +1116,7 @@ __global__ __launch_bounds__(64 * GO_NW) void k_gn_apply_out(int C, int HW, int 
         const int u = c - c0, g = c / cpg;
         const float xe = u < 4 ? xv[u] : ldx(x + ((size_t)b * C + c) * HW + pc);
         const float re = u < 4 ? rv[u] : (post ? post[((size_t)b * C + c) * HW + pc] : 0.0f);
-        const float sc1 = sso ? ss[(size_t)b * 2 * C + c] + 1.0f : 0.0f, sh = sso ? ss[(size_t)b * 2 * C + C + c] : 0.0f;
+        const float sc1 = gn_scale1(sso, ss, b, C, c), sh = gn_shift(sso, ss, b, C, c);
         float v = gn_silu1(xe, st[g][0], st[g][1], gamma[c], beta[c], sso, sc1, sh);
         if (post) v += re;
 #pragma unroll
@@ -1279,21 +1245,30 @@ __global__ __launch_bounds__(256) void k_linear(int in, int out, const float *__
     float s = 0.0f;
     for (int i = lane; i < in; i += 64) {
         float v = xb[i];
-        if (act_in == 1) v = v / (1.0f + expf(-v));
+        if (act_in == 1) v = silu_exact(v);
         s += wo[i] * v;
     }
     for (int off = 32; off > 0; off >>= 1) s += __shfl_down(s, off, 64);
     if (lane == 0) {
         float v = s + (bias ? bias[o] : 0.0f);
-        if (act_out == 1) v = 0.5f * v * (1.0f + erff(v * 0.70710678118654752f));   // nn.GELU (erf)
+        if (act_out == 1) v = gelu_exact(v);
         y[(size_t)b * out + o] = v;
     }
 }
 
+// SinusoidalPosEmb: the argument of element i (of dim / 2) at step t, (float)t exp(i neg_emb) in fp32; the
+// caller stores sinf | cosf of it in the two halves (time_mlp_rows, k_time_mlp_b; k_sinusoidal restates the
+// two lines: there the call moves the load of t in front of the expf)
+__device__ __forceinline__ float sin_emb_arg(int i, float neg_emb, int64_t t)
+{
+    const float f = expf((float)i * neg_emb);
+    return (float)t * f;
+}
 __global__ void k_sinusoidal(int dim, float neg_emb, const int64_t *__restrict__ t, float *__restrict__ y)
 {
     const int i = threadIdx.x, b = blockIdx.x, half = dim / 2;
     if (i >= half) return;
+    // sin_emb_arg, written out
     const float f = expf((float)i * neg_emb);
     const float arg = (float)t[b] * f;
     y[(size_t)b * dim + i] = sinf(arg);
@@ -1318,7 +1293,7 @@ __device__ __forceinline__ float wave_dot(const float *__restrict__ w, const flo
             const int i = i0 + lane + 64 * u;
             if (i < in) {
                 float v = x[i];
-                if (silu) v = v / (1.0f + expf(-v));
+                if (silu) v = silu_exact(v);
                 s += wv[u] * v;
             }
         }
@@ -1345,8 +1320,7 @@ __device__ __forceinline__ void time_mlp_rows(const TmArgs &m, int bx, int b, fl
     const int tid = threadIdx.x, lane = tid & 63, wv = tid >> 6;
     const int half = dim / 2;
     for (int i = tid; i < half; i += 256) {
-        const float f = expf((float)i * neg_emb);
-        const float arg = (float)t[b] * f;
+        const float arg = sin_emb_arg(i, neg_emb, t[b]);
         e[i] = sinf(arg);
         e[half + i] = cosf(arg);
     }
@@ -1366,7 +1340,7 @@ __device__ __forceinline__ void time_mlp_rows(const TmArgs &m, int bx, int b, fl
             for (int i = 0; i < dim; ++i) s += wr[i] * e[i];
         }
         const float v = s + b1[o];
-        h[o] = 0.5f * v * (1.0f + erff(v * 0.70710678118654752f));
+        h[o] = gelu_exact(v);
     }
     __syncthreads();
     const int o = bx * TM_ROWS + wv;
@@ -1382,7 +1356,9 @@ __global__ __launch_bounds__(256) void k_time_mlp(TmArgs m)
 
 // Large batches (the configs[4] tile batch, hundreds of samples): the time MLP for TMB samples per
 // workgroup, so the hidden layer's weights are read once per sample block instead of once per
-// (row block, sample); per sample the arithmetic is time_mlp_rows' (bit for bit k_time_mlp's).
+// (row block, sample); per sample the arithmetic is time_mlp_rows' (bit for bit k_time_mlp's: the embedding
+// argument is sin_emb_arg; the hidden row's dot product and GELU restate time_mlp_rows' lines, since calls to
+// a shared dot product or to gelu_exact change this kernel's text).
 constexpr int TMB = 8;
 constexpr int TMB_RW = 8;                             // k_time_mlp_b: second-layer rows per wave
 __global__ __launch_bounds__(256) void k_time_mlp_b(TmArgs m, int B)
@@ -1393,8 +1369,7 @@ __global__ __launch_bounds__(256) void k_time_mlp_b(TmArgs m, int B)
     const int tid = threadIdx.x, lane = tid & 63, wv = tid >> 6, half = dim / 2;
     for (int idx = tid; idx < nb * half; idx += 256) {
         const int bb = idx / half, i = idx - bb * half;
-        const float f = expf((float)i * m.neg_emb);
-        const float arg = (float)m.t[b0 + bb] * f;
+        const float arg = sin_emb_arg(i, m.neg_emb, m.t[b0 + bb]);
         tmb_sm[bb * ld + i] = sinf(arg);
         tmb_sm[bb * ld + half + i] = cosf(arg);
     }
@@ -1416,7 +1391,7 @@ __global__ __launch_bounds__(256) void k_time_mlp_b(TmArgs m, int B)
                 for (int i = 0; i < dim; ++i) s += wr[i] * e[i];
             }
             const float v = s + m.b1[o];
-            tmb_sm[bb * ld + dim + o] = 0.5f * v * (1.0f + erff(v * 0.70710678118654752f));
+            tmb_sm[bb * ld + dim + o] = 0.5f * v * (1.0f + erff(v * 0.70710678118654752f));   // gelu_exact, written out
         }
     }
     __syncthreads();
@@ -1443,6 +1418,11 @@ struct LinMulti {
     int start[LM_MAX + 1];
     int n;
 };
+// row o's bias of a linear whose bias pointer is bj (null: none); called with L.b[j] (lsm_rows,
+// k_linear_silu_multi, k_linear_silu_multi_b, k_wdot_silu_b).  The row lookup next to each call
+// (`while (go >= L.start[j + 1]) ++j; o = go - L.start[j]`) stays in the callers: a helper that reads L.start
+// takes a reference into the kernels' by-value LinMulti, which changes their text.
+__device__ __forceinline__ float lm_bias(const float *bj, int o) { return bj ? bj[o] : 0.0f; }
 // LSM_RPW rows of the multi-linear per wave, their weight loads issued together; each row's
 // arithmetic is wave_dot's (same order: k_linear_silu_multi's results bit for bit).  Workgroup blk
 // of sample b: rows [blk * 4 * LSM_RPW, (blk + 1) * 4 * LSM_RPW).  Used as a side job of the
@@ -1465,7 +1445,7 @@ __device__ __forceinline__ void lsm_rows(int in, const float *__restrict__ x, co
         const int o = go - L.start[j];
         wr[r] = L.w[j] + (size_t)o * in;
         yo[r] = g0 + r < gend ? L.y[j] + (size_t)b * L.out[j] + o : nullptr;
-        bo[r] = L.b[j] ? L.b[j][o] : 0.0f;
+        bo[r] = lm_bias(L.b[j], o);
     }
     const float *xb = x + (size_t)b * in;
     float s[RPW];
@@ -1482,7 +1462,7 @@ __device__ __forceinline__ void lsm_rows(int in, const float *__restrict__ x, co
             const int i = i0 + lane + 64 * u;
             if (i < in) {
                 float v = xb[i];
-                v = v / (1.0f + expf(-v));
+                v = silu_exact(v);
 #pragma unroll
                 for (int r = 0; r < RPW; ++r) s[r] += wv4[r][u] * v;
             }
@@ -1506,7 +1486,7 @@ __global__ __launch_bounds__(256) void k_linear_silu_multi_b(int in, int B, cons
     const int b0 = blockIdx.y * LSB, nb = min(LSB, B - b0);
     for (int idx = threadIdx.x; idx < nb * in; idx += 256) {
         float v = x[(size_t)b0 * in + idx];
-        lsb_sm[idx] = v / (1.0f + expf(-v));
+        lsb_sm[idx] = silu_exact(v);
     }
     __syncthreads();
     const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6, gend = L.start[L.n];
@@ -1517,7 +1497,7 @@ __global__ __launch_bounds__(256) void k_linear_silu_multi_b(int in, int B, cons
         while (go >= L.start[j + 1]) ++j;
         const int o = go - L.start[j];
         const float *w = L.w[j] + (size_t)o * in;
-        const float bo = L.b[j] ? L.b[j][o] : 0.0f;
+        const float bo = lm_bias(L.b[j], o);
         float wv4[4];                                 // in <= 256 (host check): one chunk, loaded once
 #pragma unroll
         for (int u = 0; u < 4; ++u) wv4[u] = w[min(lane + 64 * u, in - 1)];
@@ -1619,7 +1599,7 @@ __global__ __launch_bounds__(256) void k_wdot_silu_b(int B, const float *__restr
 #pragma unroll
         for (int q = 0; q < 16; ++q) {
             const int idx = (it + q) * 256 + tid;
-            xs[idx >> 8][(idx & 63) * 4 + ((idx >> 6) & 3)] = v[q] / (1.0f + expf(-v[q]));
+            xs[idx >> 8][(idx & 63) * 4 + ((idx >> 6) & 3)] = silu_exact(v[q]);
         }
     }
     __syncthreads();
@@ -1632,7 +1612,7 @@ __global__ __launch_bounds__(256) void k_wdot_silu_b(int B, const float *__restr
         int j = 0;
         while (go >= L.start[j + 1]) ++j;
         const int o = go - L.start[j];
-        if (lane < nb) L.y[j][(size_t)b * L.out[j] + o] = res + (L.b[j] ? L.b[j][o] : 0.0f);
+        if (lane < nb) L.y[j][(size_t)b * L.out[j] + o] = res + lm_bias(L.b[j], o);
     }
 }
 
@@ -1644,7 +1624,7 @@ __global__ __launch_bounds__(256) void k_linear_silu_multi(int in, const float *
     while (go >= L.start[j + 1]) ++j;
     const int o = go - L.start[j];
     const float s = wave_dot(L.w[j] + (size_t)o * in, x + (size_t)b * in, in, lane, true);
-    if (lane == 0) L.y[j][(size_t)b * L.out[j] + o] = s + (L.b[j] ? L.b[j][o] : 0.0f);
+    if (lane == 0) L.y[j][(size_t)b * L.out[j] + o] = s + lm_bias(L.b[j], o);
 }
 
 // The U-Net's first launch (Unet.forward, diffusion.py:276-279): init_conv (k_conv_ig tiles,
@@ -2743,6 +2723,30 @@ __device__ __forceinline__ void c3_epilogue(const C3Args &a, f32x16 (&acc)[2][2]
     }
 }
 
+// the halo gather of the two halo-staged convs' fp32 input (k_conv3_bf16 without IN8, k_conv3_f32), called from
+// their hload / hsrc lambdas with the argument struct's fields by value.
+// c3_hload: one halo item's 8 channels.  s: the item's source b << 20 | pix (~0u: none); unconditional loads
+// at 32-bit offsets from the chunk's resource rs, the channel's plane in the soffset; an empty item or a
+// channel group past cin (!cok) gets an offset past the resource and loads zeros.
+// c3_hsrc: the resource of the 8-channel group starting at channel c (of x below cin1, of x2 above), its
+// sample stride in bytes and whether the group exists (cin = cin1 + cin2, the caller's own sum).
+__device__ __forceinline__ void c3_hload(unsigned s, const __amdgpu_buffer_rsrc_t &rs, unsigned cstride, bool cok,
+                                         int plane, float (&v)[8])
+{
+    const int vo = (s != ~0u && cok) ? (int)((s >> 20) * cstride + (s & 0xfffff) * 4u) : (int)0x80000000u;
+#pragma unroll
+    for (int j = 0; j < 8; ++j)
+        v[j] = __builtin_bit_cast(float, __builtin_amdgcn_raw_buffer_load_b32(rs, vo, j * plane * 4, 0));
+}
+__device__ __forceinline__ __amdgpu_buffer_rsrc_t c3_hsrc(int c, int cin1, int cin2, int cin, int plane, const float *x,
+                                                          const float *x2, unsigned &cstride, bool &cok)
+{
+    const bool lo = c < cin1;
+    cok = c < cin;
+    cstride = (unsigned)(lo ? cin1 : cin2) * (unsigned)plane * 4u;
+    const float *base = !cok ? x : lo ? x + (size_t)c * plane : x2 + (size_t)(c - cin1) * plane;
+    return __builtin_amdgcn_make_buffer_rsrc(const_cast<float *>(base), (short)0, 0x7fffffff, 0x00020000);
+}
 template <int MODE, bool IN8 = false>
 __global__ __launch_bounds__(256, 2) void k_conv3_bf16(C3Args a)
 {
@@ -2759,7 +2763,7 @@ __global__ __launch_bounds__(256, 2) void k_conv3_bf16(C3Args a)
     const int cin = d.cin1 + d.cin2;
     // halo items: wave wv gathers the chunk's 8-channel group wv (so the source tensor and the
     // channel base are wave-uniform) for halo rows q = lane + 64 k; the source pixel is packed
-    // b << 20 | pix (~0u: outside the batch or past the halo -> zeros)
+    // b << 20 | pix (~0u: outside the batch or past the halo -> zeros).  Twin: k_conv3_f32's loop, other q
     unsigned it_src[C3_NI];
 #pragma unroll
     for (int k = 0; k < C3_NI; ++k) {
@@ -2789,22 +2793,14 @@ __global__ __launch_bounds__(256, 2) void k_conv3_bf16(C3Args a)
     // (fp32 input) the chunk's 8-channel group of the wave through a buffer resource on its first
     // channel plane: the item's sample / pixel offset in a VGPR, the channel j's plane offset in the
     // SGPR soffset (no per-load address arithmetic); an item outside the image, or channels past
-    // cin, get an offset past the resource and load zeros (no per-element select)
+    // cin, get an offset past the resource and load zeros (no per-element select): c3_hsrc, c3_hload
     const int wvu = __builtin_amdgcn_readfirstlane(wv);
     auto hsrc = [&](int cc, unsigned &cstride, bool &cok) -> __amdgpu_buffer_rsrc_t {
         const int c = cc * BF_BK + 8 * wvu;
-        const bool lo = c < d.cin1;
-        cok = c < cin;
-        cstride = (unsigned)(lo ? d.cin1 : d.cin2) * (unsigned)a.plane * 4u;
-        const float *base = !cok ? a.x : lo ? a.x + (size_t)c * a.plane : a.x2 + (size_t)(c - d.cin1) * a.plane;
-        return __builtin_amdgcn_make_buffer_rsrc(const_cast<float *>(base), (short)0, 0x7fffffff, 0x00020000);
+        return c3_hsrc(c, d.cin1, d.cin2, cin, a.plane, a.x, a.x2, cstride, cok);
     };
     auto hload = [&](int k, const __amdgpu_buffer_rsrc_t &rs, unsigned cstride, bool cok, float (&v)[8]) {
-        const unsigned s = it_src[k];
-        const int vo = (s != ~0u && cok) ? (int)((s >> 20) * cstride + (s & 0xfffff) * 4u) : (int)0x80000000u;
-#pragma unroll
-        for (int j = 0; j < 8; ++j)
-            v[j] = __builtin_bit_cast(float, __builtin_amdgcn_raw_buffer_load_b32(rs, vo, j * a.plane * 4, 0));
+        c3_hload(it_src[k], rs, cstride, cok, a.plane, v);
     };
     auto hpack = [&](const float (&v)[8]) -> bf16x8 {
         bf16x8 h;
@@ -2829,7 +2825,7 @@ __global__ __launch_bounds__(256, 2) void k_conv3_bf16(C3Args a)
     };
     auto wstash = [&](int buf, const bf16x8 &v) { *reinterpret_cast<bf16x8 *>(&Ws[buf][wn][wq]) = v; };
     // MFMA role: wave wv owns pixels wv*64 + mb*32 + (lane & 31), mb = 0, 1; bit ky*3+kx of tmask[mb]
-    // says whether tap (ky, kx) stays inside the image for this lane's pixel
+    // says whether tap (ky, kx) stays inside the image for this lane's pixel.  Twin: k_conv3_f32's loop
     int pl[2];
     unsigned tmask[2];
 #pragma unroll
@@ -2965,7 +2961,8 @@ __global__ __launch_bounds__(256, 2) void k_conv3_f32(C3Args a)
     const int m0 = blockIdx.x * C3_BM, n0 = blockIdx.y * C3_BN;
     const int cin = d.cin1 + d.cin2;
     // halo items: octet ho of the chunk for rows q = lane + 64 (2 k + (wv >> 1)); source pixel packed
-    // b << 20 | pix as in k_conv3_bf16 (~0u: outside the batch or past the halo -> zeros)
+    // b << 20 | pix as in k_conv3_bf16 (~0u: outside the batch or past the halo -> zeros).  Twin:
+    // k_conv3_bf16's loop, other q
     const int ho = wv & 1;
     unsigned it_src[C3F_NI];
 #pragma unroll
@@ -2980,22 +2977,14 @@ __global__ __launch_bounds__(256, 2) void k_conv3_f32(C3Args a)
         }
         it_src[k] = in ? ((unsigned)b << 20 | (unsigned)pix) : ~0u;
     }
-    // the octet's channels through a buffer resource on its first plane, as k_conv3_bf16's gather
+    // the octet's channels through a buffer resource on its first plane: k_conv3_bf16's gather (c3_hsrc, c3_hload)
     const int hou = __builtin_amdgcn_readfirstlane(ho);
     auto hsrc = [&](int cc, unsigned &cstride, bool &cok) -> __amdgpu_buffer_rsrc_t {
         const int c = cc * C3F_BK + 8 * hou;
-        const bool lo = c < d.cin1;
-        cok = c < cin;
-        cstride = (unsigned)(lo ? d.cin1 : d.cin2) * (unsigned)a.plane * 4u;
-        const float *base = !cok ? a.x : lo ? a.x + (size_t)c * a.plane : a.x2 + (size_t)(c - d.cin1) * a.plane;
-        return __builtin_amdgcn_make_buffer_rsrc(const_cast<float *>(base), (short)0, 0x7fffffff, 0x00020000);
+        return c3_hsrc(c, d.cin1, d.cin2, cin, a.plane, a.x, a.x2, cstride, cok);
     };
     auto hload = [&](int k, const __amdgpu_buffer_rsrc_t &rs, unsigned cstride, bool cok, float (&v)[8]) {
-        const unsigned s = it_src[k];
-        const int vo = (s != ~0u && cok) ? (int)((s >> 20) * cstride + (s & 0xfffff) * 4u) : (int)0x80000000u;
-#pragma unroll
-        for (int j = 0; j < 8; ++j)
-            v[j] = __builtin_bit_cast(float, __builtin_amdgcn_raw_buffer_load_b32(rs, vo, j * a.plane * 4, 0));
+        c3_hload(it_src[k], rs, cstride, cok, a.plane, v);
     };
     auto hstore = [&](int buf, int k, const float (&v)[8]) {
         const int q = lane + 64 * (2 * k + (wv >> 1));
@@ -3019,6 +3008,7 @@ __global__ __launch_bounds__(256, 2) void k_conv3_f32(C3Args a)
         return ok ? v : float4{0.0f, 0.0f, 0.0f, 0.0f};
     };
     auto wstash = [&](int buf, const float4 &v) { *reinterpret_cast<float4 *>(&Ws[buf][wn][wq]) = v; };
+    // pixels and tap masks.  Twin: k_conv3_bf16's loop
     int pl[2];
     unsigned tmask[2];
 #pragma unroll
@@ -4260,13 +4250,13 @@ int rdq_conv2d_bf16_gn_silu8(const rdq_conv_desc *d, const float *x, const float
         return RDQ_E_INVALID;
     const int HW = c.HW;
     if (c.yb && HW % 2 == 0)
-        hipLaunchKernelGGL(k_gn_apply8x2, dim3((HW + 511) / 512, d->B * G), dim3(256), 0, st,
+        hipLaunchKernelGGL(HIP_KERNEL_NAME(k_gn_apply8<2, __bf16>), dim3((HW + 511) / 512, d->B * G), dim3(256), 0, st,
                            d->cout, HW, G, c.yb, gamma, beta, scale_shift, c.gnp, eps, static_cast<__bf16 *>(y8), C3_BM);
     else if (c.yb)
-        hipLaunchKernelGGL(HIP_KERNEL_NAME(k_gn_apply8<__bf16>), dim3((HW + 255) / 256, d->B * G), dim3(256), 0, st, d->cout,
+        hipLaunchKernelGGL(HIP_KERNEL_NAME(k_gn_apply8<1, __bf16>), dim3((HW + 255) / 256, d->B * G), dim3(256), 0, st, d->cout,
                            HW, G, c.yb, gamma, beta, scale_shift, c.gnp, eps, static_cast<__bf16 *>(y8), C3_BM);
     else
-        hipLaunchKernelGGL(HIP_KERNEL_NAME(k_gn_apply8<float>), dim3((HW + 255) / 256, d->B * G), dim3(256), 0, st, d->cout,
+        hipLaunchKernelGGL(HIP_KERNEL_NAME(k_gn_apply8<1, float>), dim3((HW + 255) / 256, d->B * G), dim3(256), 0, st, d->cout,
                            HW, G, c.y, gamma, beta, scale_shift, c.gnp, eps, static_cast<__bf16 *>(y8), C3_BM);
     RDQ_CHECK(hipGetLastError());
     return 0;
