@@ -139,6 +139,13 @@ SIGNATURES = {
     "rdq_smooth_reg_forward": (c_int32, [c_int32, c_int32, c_int32, c_int32, c_void_p, c_void_p, c_void_p]),
     "rdq_smooth_reg_backward": (c_int32, [c_int32, c_int32, c_int32, c_int32, c_void_p, c_void_p,
                                           c_void_p, c_void_p]),
+    # include/red_diffeq_misfit.h
+    "rdq_misfit_workspace_bytes": (c_size_t, [c_int32, c_int32, c_int32, c_int32, c_int32]),
+    "rdq_misfit_coef_bytes": (c_size_t, [c_int32, c_int32, c_int32, c_int32]),
+    "rdq_misfit_forward": (c_int32, [c_int32, c_int32, c_int32, c_int32, c_int32, c_float, c_void_p, c_void_p,
+                                     c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p]),
+    "rdq_misfit_backward": (c_int32, [c_int32, c_int32, c_int32, c_int32, c_int32, c_float, c_void_p, c_void_p,
+                                      c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p]),
     # include/red_diffeq_unet.h
     "rdq_conv2d_ws_bytes": (c_size_t, [ctypes.POINTER(ConvDesc)]),
     "rdq_conv2d_tickets": (c_size_t, [ctypes.POINTER(ConvDesc)]),

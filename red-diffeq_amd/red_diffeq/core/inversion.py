@@ -1,8 +1,8 @@
 """InversionEngine (reference red_diffeq/core/inversion.py:12-129), same API and loop order.
 
 Per iteration: [diffusion: eps_x0 ~ N(0,1); x0 = mu + sigma_x0 eps_x0] -> seis = fwi_forward(
-x0[:, :, 1:-1, 1:-1]) -> L1 misfit -> regulariser -> backward (HIP adjoint) -> Adam -> clamp to
-[-1,1] -> cosine LR step -> metrics.  RNG draw order matches the reference
+x0[:, :, 1:-1, 1:-1]) -> data misfit (L1 unless misfit= says otherwise) -> regulariser -> backward
+(HIP adjoint) -> Adam -> clamp to [-1,1] -> cosine LR step -> metrics.  RNG draw order matches the reference
 (eps_x0, then the regulariser's t, then eps).
 
 Shot-parallel inversion: when ``fwi_forward.shots`` covers a subset of the sources
@@ -30,7 +30,7 @@ from ..utils.data_trans import add_noise_to_seismic, missing_trace
 from ..utils.data_trans import v_normalize
 from ..utils.ssim import SSIM
 from .fused import CosineLR, FusedAdamClamp, metrics as fused_metrics
-from .losses import LossCalculator
+from .losses import LossCalculator, check_misfit, global_norm
 from .metrics import MetricsCalculator
 
 
@@ -248,7 +248,9 @@ class InversionEngine:
 
     def optimize(self, mu: torch.Tensor, mu_true: torch.Tensor, y: torch.Tensor, fwi_forward, ts: int = 300,
                  lr: float = 0.03, reg_lambda: float = 0.01, noise_std: float = 0.0, noise_type: str = "gaussian",
-                 missing_number: int = 0, regularization: Optional[str] = None, process_group=None):
+                 missing_number: int = 0, regularization: Optional[str] = None, process_group=None,
+                 misfit: str = "l1", huber_delta: Optional[float] = None):
+        check_misfit(misfit, huber_delta)
         if mu.shape[0] != y.shape[0]:
             raise ValueError("Batch size mismatch between velocity and seismic data")
         if regularization not in ["diffusion", "l2", "tv", "hybrid", None]:
@@ -272,7 +274,7 @@ class InversionEngine:
         # K12 computes MAE / RMSE / SSIM in one launch when the caller's ssim_loss is the reference's
         # SSIM; any other module is called per model as the reference's MetricsCalculator does
         metrics_calc = None if k12_covers(self.ssim_loss) else MetricsCalculator(self.ssim_loss)
-        loss_calc = LossCalculator(self.regularization_method)
+        loss_calc = LossCalculator(self.regularization_method, misfit, huber_delta)
         keys = ("total_losses", "obs_losses", "reg_losses", "ssim", "mae", "rmse")
         # per-iteration histories stay on the device; ONE copy to the host after the loop (the
         # reference syncs six times per iteration, inversion.py:97-111)
@@ -291,8 +293,7 @@ class InversionEngine:
         sharded = shots is not None and dist.is_available() and dist.is_initialized()
         if shots is not None:
             if sharded:   # global observation count from the full (replicated) mask: no communication
-                nobs = mask.reshape(B, -1).sum(1).clamp(min=1.0)
-                loss_calc.global_nobs = nobs
+                loss_calc.global_nobs = global_norm(misfit, y, mask)   # ncc: the live-trace count
             y = y[:, shots[0]:shots[1]].contiguous()
             mask = mask[:, shots[0]:shots[1]].contiguous()
             if missing_number == 0:

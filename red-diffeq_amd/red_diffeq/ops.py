@@ -42,6 +42,8 @@ torch.compile see them as ordinary operators instead of opaque ctypes calls.
     sample_step(x_t, t, out, noise, tables, ...) writes x_next (and x_start_out / t_out): the fused reverse step
   loop(include/red_diffeq_loop.h)
     l1_misfit / l1_misfit_backward, smooth_reg / smooth_reg_backward, metrics, adam_clamp_
+  misfits beyond L1 (include/red_diffeq_misfit.h)
+    misfit(pred, y, mask, kind, delta) -> (loss, norm, coef), misfit_backward(..., norm, coef, gout, kind, delta)
 
 No CPU implementation is registered: a CPU tensor reaching an op raises (no fallback).
 """
@@ -1483,6 +1485,79 @@ def l1_misfit_backward(pred: Tensor, y: Tensor, mask: Optional[Tensor], nobs: Te
 @l1_misfit_backward.register_fake
 def _(pred, y, mask, nobs, gout):
     return torch.empty_like(pred, dtype=torch.float32)
+
+
+MISFIT_KINDS = {"l2": 1, "huber": 2, "ncc": 3}                           # RDQ_MISFIT_*
+
+
+def _misfit_dims(pred: Tensor, kind: int):
+    """(B, ns, nt, ng) of a misfit call: the record's own for NCC (4-D), and for the elementwise kinds any
+    [B, ...] shape as one row of n elements per model."""
+    if kind not in MISFIT_KINDS.values():
+        raise ValueError(f"misfit: unknown kind {kind}")
+    if pred.dim() < 2 or pred.numel() == 0:
+        raise ValueError("misfit: pred must be a non-empty [B, ...] tensor")
+    if kind == MISFIT_KINDS["ncc"]:
+        if pred.dim() != 4:
+            raise ValueError("misfit: the ncc misfit needs a (B, ns, nt, ng) record")
+        return tuple(pred.shape)
+    return pred.shape[0], 1, 1, pred.numel() // pred.shape[0]
+
+
+@torch.library.custom_op(f"{LIB}::misfit", mutates_args=())
+def misfit(pred: Tensor, y: Tensor, mask: Optional[Tensor], kind: int, delta: float) -> Tuple[Tensor, Tensor, Tensor]:
+    """K13 forward (include/red_diffeq_misfit.h): kind 1 L2, 2 Huber (delta), 3 NCC -> (loss, norm, coef);
+    norm is nobs (L2, Huber) or the live-trace count (NCC), coef the NCC's (inv, r, J) per trace, float64
+    (B, ns, ng, 3) (empty for the other kinds)."""
+    _hip.require_device(pred, y, mask)
+    B, ns, nt, ng = _misfit_dims(pred, kind)
+    if y.shape != pred.shape or (mask is not None and mask.shape != pred.shape):
+        raise ValueError("misfit: y and mask must have pred's shape")
+    pred, y = pred.float().contiguous(), y.float().contiguous()
+    mask = mask.float().contiguous() if mask is not None else None
+    L = _hip.lib()
+    loss = torch.empty(B, dtype=torch.float32, device=pred.device)
+    norm = torch.empty(B, dtype=torch.float32, device=pred.device)
+    coef = torch.empty((B, ns, ng, 3) if kind == MISFIT_KINDS["ncc"] else (0,), dtype=torch.float64, device=pred.device)
+    ws = torch.empty(int(L.rdq_misfit_workspace_bytes(kind, B, ns, nt, ng)), dtype=torch.uint8, device=pred.device)
+    _hip.check(L.rdq_misfit_forward(kind, B, ns, nt, ng, delta, _hip.ptr(pred), _hip.ptr(y), _hip.ptr(mask),
+                                    _hip.ptr(loss), _hip.ptr(norm), _hip.ptr(coef), _hip.ptr(ws), _hip.stream_of(pred)), "rdq_misfit_forward")
+    return loss, norm, coef
+
+
+@misfit.register_fake
+def _(pred, y, mask, kind, delta):
+    B = pred.shape[0]
+    shape = (B, pred.shape[1], pred.shape[3], 3) if kind == MISFIT_KINDS["ncc"] else (0,)
+    return pred.new_empty(B, dtype=torch.float32), pred.new_empty(B, dtype=torch.float32), \
+        pred.new_empty(shape, dtype=torch.float64)
+
+
+@torch.library.custom_op(f"{LIB}::misfit_backward", mutates_args=())
+def misfit_backward(pred: Tensor, y: Tensor, mask: Optional[Tensor], norm: Tensor, coef: Tensor, gout: Tensor,
+                    kind: int, delta: float) -> Tensor:
+    """K13 backward: dloss / dpred for the upstream gout (B,), with the forward's norm (or a sharded survey's
+    global one) and, for NCC, the forward's coef."""
+    _hip.require_device(pred, y, mask, norm, coef, gout)
+    B, ns, nt, ng = _misfit_dims(pred, kind)
+    pred, y = pred.float().contiguous(), y.float().contiguous()
+    mask = mask.float().contiguous() if mask is not None else None
+    if kind == MISFIT_KINDS["ncc"] and (coef.dtype != torch.float64 or coef.shape != (B, ns, ng, 3)):
+        raise ValueError("misfit_backward: coef must be the forward's float64 (B, ns, ng, 3)")
+    if norm.numel() != B or gout.numel() != B:
+        raise ValueError("misfit_backward: norm and gout must have B elements")
+    dpred = torch.empty_like(pred)
+    # named, so that the copy of an expanded (stride-0) gout lives until the launch is enqueued
+    norm, gout, coef = norm.float().contiguous(), gout.float().contiguous(), coef.contiguous()
+    _hip.check(_hip.lib().rdq_misfit_backward(kind, B, ns, nt, ng, delta, _hip.ptr(pred), _hip.ptr(y), _hip.ptr(mask),
+                                              _hip.ptr(norm), _hip.ptr(coef), _hip.ptr(gout),
+                                              _hip.ptr(dpred), _hip.stream_of(pred)), "rdq_misfit_backward")
+    return dpred
+
+
+@misfit_backward.register_fake
+def _(pred, y, mask, norm, coef, gout, kind, delta):
+    return torch.empty_like(pred, dtype=torch.float32, memory_format=torch.contiguous_format)
 
 
 @torch.library.custom_op(f"{LIB}::smooth_reg", mutates_args=())

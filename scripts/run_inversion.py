@@ -14,7 +14,9 @@ Differences by design: checkpoints are read with torch.load(weights_only=True); 
 `accelerate` wrapper (it only wraps GaussianDiffusion.forward, the training loss, which the
 inversion never calls); under torchrun (WORLD_SIZE > 1) the shots are sharded over the ranks
 (one RCCL all-reduce of the data-term gradient per iteration) and rank 0 writes the
-results.
+results.  Two options the reference lacks, --misfit {l1,l2,huber,ncc} and --huber_delta (config keys
+optimization.misfit / optimization.huber_delta, both optional: without them the run is the reference's
+L1), choose the data misfit.
 """
 import argparse
 import os
@@ -33,6 +35,7 @@ from tqdm import tqdm  # noqa: E402
 from red_diffeq import (FWIForward, GaussianDiffusion, InversionEngine, SSIM, Unet, get_config,  # noqa: E402
                         load_config, prepare_initial_model, s_normalize_none, save_config, v_denormalize)
 from red_diffeq.config.config_dict import ConfigDict  # noqa: E402
+from red_diffeq.core.losses import MISFITS, check_misfit  # noqa: E402
 
 
 def _dist():
@@ -116,7 +119,9 @@ def process_batch(batch_start, batch_end, seis_mmap, vel_mmap, config, inversion
         init, vel, seis, fwi_forward, ts=config.optimization.ts, lr=config.optimization.lr,
         reg_lambda=config.optimization.reg_lambda, noise_std=config.optimization.noise_std,
         noise_type=config.optimization.noise_type, missing_number=config.optimization.missing_number,
-        regularization=reg if reg and reg != "none" else None)
+        regularization=reg if reg and reg != "none" else None,
+        misfit=getattr(config.optimization, "misfit", "l1"),
+        huber_delta=getattr(config.optimization, "huber_delta", None))
     return mu, results, init, vel
 
 
@@ -193,6 +198,8 @@ def main(argv=None) -> None:
     p.add_argument("--sigma", type=float)
     p.add_argument("--sigma_x0", type=float)
     p.add_argument("--missing_number", type=int)
+    p.add_argument("--misfit", choices=list(MISFITS), help="data misfit (config: optimization.misfit, else l1)")
+    p.add_argument("--huber_delta", type=float, help="threshold of --misfit huber (config: optimization.huber_delta)")
     p.add_argument("--batch_size", type=int)
     p.add_argument("--experiment_name", type=str)
     p.add_argument("--results_dir", type=Path)
@@ -206,6 +213,7 @@ def main(argv=None) -> None:
                  "reg_lambda": ("optimization", "reg_lambda"), "noise_type": ("optimization", "noise_type"),
                  "noise_std": ("optimization", "noise_std"), "sigma": ("optimization", "sigma"),
                  "sigma_x0": ("optimization", "sigma_x0"), "missing_number": ("optimization", "missing_number"),
+                 "misfit": ("optimization", "misfit"), "huber_delta": ("optimization", "huber_delta"),
                  "batch_size": ("data", "batch_size"), "experiment_name": ("experiment", "name"),
                  "results_dir": ("experiment", "results_dir"), "random_seed": ("experiment", "random_seed"),
                  "openfwi_families": ("data", "openfwi_families"), "sample_index": ("data", "sample_index")}
@@ -213,6 +221,10 @@ def main(argv=None) -> None:
         v = getattr(a, arg)
         if v is not None:
             setattr(getattr(config, sec), key, str(v) if isinstance(v, Path) else v)
+    # the misfit the run uses goes into the saved config (the reference's YAMLs carry neither key: l1)
+    config.optimization.misfit = getattr(config.optimization, "misfit", "l1")
+    config.optimization.huber_delta = getattr(config.optimization, "huber_delta", None)
+    check_misfit(config.optimization.misfit, config.optimization.huber_delta)
     run_experiment(config)
     if dist.is_initialized():
         dist.destroy_process_group()
