@@ -28,12 +28,40 @@ extern "C" {
 #define RDQ_IN_UPSAMPLE2 1
 #define RDQ_IN_UNSHUFFLE2 2
 
+/* The contract of every conv entry point below.  With `in` the logical (B, cin1+cin2, H, W) input,
+ * ZERO outside the image:
+ *   y[b][n][oh][ow] = bias[n] + residual[b][n][oh][ow]
+ *                     + sum over c, ky < kh, kx < kw of  w[n][c][ky][kx] * in[b][c][oh + ky - pad][ow + kx - pad]
+ * The output is always H x W, and the one `pad` serves both axes (in torch terms:
+ * F.conv2d(F.pad(in, (pad, kw-1-pad, pad, kh-1-pad)), w), a negative pad cropping).  This is
+ * nn.Conv2d(stride 1, dilation 1, groups 1, zero padding `pad`) exactly when kh = kw = 2 pad + 1; for any
+ * other filter (even sizes, kh != kw, pad != (k-1)/2) the kernels compute the definition above, which is
+ * NOT nn.Conv2d's result (that output would not be H x W).  The Python wrappers refuse such modules. */
 typedef struct rdq_conv_desc {
     int32_t B, cin1, cin2, H, W, cout, kh, kw, pad, in_mode;
 } rdq_conv_desc;
 
-/* y = conv2d(input, w, bias, stride 1, padding pad) [+ residual]   (nn.Conv2d, implicit GEMM on
- * fp32 MFMA v_mfma_f32_16x16x4_f32).  w: [cout][cin1+cin2][kh][kw]; bias/residual nullable.
+/* Which kernel family a descriptor takes under the current options (a pure host function; rdq_conv2d and
+ * rdq_conv2d_bf16 branch on it, so a test knows which kernel it compared).  bf16 = 0: rdq_conv2d, else
+ * rdq_conv2d_bf16.
+ *   IG        implicit GEMM, any filter (k_conv_ig; split-K through k_conv_reduce when given a workspace)
+ *   CC        channel-chunk form (k_conv_cc): 3x3 (plain / nearest x2, any pad, channel counts % 8 == 0)
+ *             or 1x1 pad 0 (plain / unshuffle, channel counts % 64 == 0)
+ *   C3F       fp32 halo-staged 3x3 pad 1 (k_conv3_f32): cin % 8 == 0, cout % 64 == 0, W <= 72, and at
+ *             least RDQ_UNET_OPT_CONV3F_MIN_TILES tiles; it takes precedence over CC
+ *   C3_BF16   bf16 halo-staged 3x3 pad 1 (k_conv3_bf16): the same shapes, RDQ_UNET_OPT_CONV3_MIN_TILES,
+ *             unless RDQ_UNET_OPT_BF16_PER_TAP
+ *   BF16_TAP  bf16 per-tap kernel (k_conv_bf16): every other bf16 conv */
+#define RDQ_CONV_ROUTE_INVALID 0
+#define RDQ_CONV_ROUTE_IG 1
+#define RDQ_CONV_ROUTE_CC 2
+#define RDQ_CONV_ROUTE_C3F 3
+#define RDQ_CONV_ROUTE_BF16_TAP 4
+#define RDQ_CONV_ROUTE_C3_BF16 5
+int rdq_conv2d_route(const rdq_conv_desc *d, int bf16);
+
+/* y = conv of the contract above (implicit GEMM on fp32 MFMA v_mfma_f32_16x16x4_f32).
+ * w: [cout][cin1+cin2][kh][kw]; bias/residual nullable.
  * ws (nullable) holds split-K partial slabs: rdq_conv2d_ws_bytes(d) bytes let the kernel split the
  * reduction over enough workgroups to fill the chip; a smaller (or null) ws splits less (or not).
  * tickets (nullable): rdq_conv2d_tickets(d) uint32 words that are ZERO when the call is enqueued;

@@ -664,7 +664,8 @@ __global__ __launch_bounds__(256, 2) void k_conv_cc_pair(CcArgs a, CcArgs b, int
     }
 }
 
-// channel-chunk form applies: 3x3 (any pad) or 1x1 (pad 0) filters, every channel count a multiple
+// channel-chunk form applies: 3x3 (any pad >= 0: the output stays H x W, see rdq_conv_desc's contract; it is
+// nn.Conv2d's only at pad 1) or 1x1 (pad 0) filters, every channel count a multiple
 // of the chunk (so a stage never straddles the concat seam), 16-B aligned weight rows
 bool cc_ok(const rdq_conv_desc *d)
 {
@@ -673,6 +674,7 @@ bool cc_ok(const rdq_conv_desc *d)
     const int cps = d->kh == 3 ? CcCfg<9>::CPS : CcCfg<1>::CPS;
     if (d->kh == 1 && d->pad != 0) return false;
     if (d->in_mode == RDQ_IN_UNSHUFFLE2 && d->kh != 1) return false;
+    if (d->in_mode == RDQ_IN_UPSAMPLE2 && d->kh != 3) return false;   // k_conv_cc<1, ...> gathers plain / unshuffled only
     if (d->cin1 % cps || d->cin2 % cps || cin % 4) return false;
     const int64_t lim = INT32_MAX;                 // buffer-load extents and offsets are 32-bit
     const int64_t xy = (int64_t)d->B * d->H * d->W * 4;
@@ -3607,6 +3609,7 @@ __global__ __launch_bounds__(256, (LbOcc<D, F>::N)) void k_lab_out(LabArgs a)
 static std::atomic<int> C3_BF16_RAW{1};      // RDQ_UNET_OPT_BF16_RAW
 static std::atomic<int> C3_MIN_TILES{64};    // RDQ_UNET_OPT_CONV3_MIN_TILES; tools/conv3_threshold_ab.py
 static std::atomic<int> C3F_MIN_TILES{192};  // k_conv3_f32; RDQ_UNET_OPT_CONV3F_MIN_TILES, 0 = never
+static std::atomic<int> g_bf16_per_tap{0};    // RDQ_UNET_OPT_BF16_PER_TAP
 static std::atomic<int> g_opt_gen{0};
 static int64_t conv3_tiles(const rdq_conv_desc *d)
 {
@@ -3884,16 +3887,26 @@ size_t rdq_conv2d_ws_bytes(const rdq_conv_desc *d)
 }
 
 
+// the one place that picks a conv kernel family: rdq_conv2d and rdq_conv2d_bf16 branch on it
+int rdq_conv2d_route(const rdq_conv_desc *d, int bf16)
+{
+    if (!conv_desc_ok(d)) return RDQ_CONV_ROUTE_INVALID;
+    if (bf16) return conv3_ok(d) && !g_bf16_per_tap ? RDQ_CONV_ROUTE_C3_BF16 : RDQ_CONV_ROUTE_BF16_TAP;
+    if (conv3f_ok(d)) return RDQ_CONV_ROUTE_C3F;
+    return cc_ok(d) ? RDQ_CONV_ROUTE_CC : RDQ_CONV_ROUTE_IG;
+}
+
 int rdq_conv2d(const rdq_conv_desc *d, const float *x, const float *x2, const float *w, const float *bias,
                const float *residual, float *y, void *ws, size_t ws_bytes, uint32_t *tickets, hipStream_t st)
 {
     if (!conv_in_ok(d, x, x2) || !w || !y) return RDQ_E_INVALID;
-    if (conv3f_ok(d)) {
+    const int route = rdq_conv2d_route(d, 0);
+    if (route == RDQ_CONV_ROUTE_C3F) {
         launch_conv3_f32(d, x, x2, w, bias, residual, y, nullptr, 0, st);
         RDQ_CHECK(hipGetLastError());
         return 0;
     }
-    if (cc_ok(d)) {
+    if (route == RDQ_CONV_ROUTE_CC) {
         CcArgs c = cc_args(d, ws, ws_bytes, tickets, CC_SPLIT_ANY);
         c.x = x; c.x2 = x2; c.w = w; c.bias = bias; c.res = residual; c.y = y;
         const dim3 grid = cc_grid(c);
@@ -4136,8 +4149,6 @@ size_t rdq_conv2d_bf16_ws_bytes(const rdq_conv_desc *d)
     return S > 1 ? (size_t)S * d->B * d->H * d->W * d->cout * sizeof(float) : 0;
 }
 
-static std::atomic<int> g_bf16_per_tap{0};   // RDQ_UNET_OPT_BF16_PER_TAP
-
 int rdq_unet_set_option(int32_t option, int32_t value)
 {
     std::atomic<int> *opt = nullptr;
@@ -4175,7 +4186,7 @@ int rdq_conv2d_bf16(const rdq_conv_desc *d, const float *x, const float *x2, con
                     const float *residual, float *y, void *ws, size_t ws_bytes, hipStream_t st)
 {
     if (!conv_in_ok(d, x, x2) || !wp || !y) return RDQ_E_INVALID;
-    if (conv3_ok(d) && !g_bf16_per_tap) {
+    if (rdq_conv2d_route(d, 1) == RDQ_CONV_ROUTE_C3_BF16) {
         C3Args c = c3_args(d, BF_BK);
         c.x = x; c.x2 = x2; c.w = static_cast<const __bf16 *>(wp); c.bias = bias; c.res = residual; c.y = y;
         launch_conv3_bf16(c, false, st);

@@ -147,6 +147,7 @@ SIGNATURES = {
     "rdq_misfit_backward": (c_int32, [c_int32, c_int32, c_int32, c_int32, c_int32, c_float, c_void_p, c_void_p,
                                       c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p]),
     # include/red_diffeq_unet.h
+    "rdq_conv2d_route": (c_int32, [ctypes.POINTER(ConvDesc), c_int32]),
     "rdq_conv2d_ws_bytes": (c_size_t, [ctypes.POINTER(ConvDesc)]),
     "rdq_conv2d_tickets": (c_size_t, [ctypes.POINTER(ConvDesc)]),
     "rdq_conv2d": (c_int32, [ctypes.POINTER(ConvDesc), c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p,

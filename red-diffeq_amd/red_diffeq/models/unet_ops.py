@@ -35,12 +35,34 @@ def precision(mode):
         _PREC["mode"] = old
 
 
+def conv_pad(conv):
+    """The one `pad` of rdq_conv_desc for an nn.Conv2d the kernels implement: stride 1, dilation 1, groups 1,
+    zero padding, the same integer padding on both axes and a `same`-sized output (2 pad = k - 1 on both axes:
+    include/red_diffeq_unet.h, the contract of rdq_conv_desc).  Anything else raises ValueError before any
+    device work: the kernels would compute something that is not this module's result."""
+    def pair(v):
+        return tuple(v) if isinstance(v, (tuple, list)) else (v, v)
+    if pair(conv.stride) != (1, 1) or pair(conv.dilation) != (1, 1) or conv.groups != 1:
+        raise ValueError(f"conv kernels implement stride 1, dilation 1, groups 1 only (got stride {conv.stride}, "
+                         f"dilation {conv.dilation}, groups {conv.groups})")
+    if getattr(conv, "padding_mode", "zeros") != "zeros":
+        raise ValueError(f"conv kernels implement zero padding only (got padding_mode {conv.padding_mode!r})")
+    if isinstance(conv.padding, str):
+        raise ValueError(f"conv kernels take an integer padding (got {conv.padding!r})")
+    ph, pw = pair(conv.padding)
+    if ph != pw:
+        raise ValueError(f"conv kernels take one padding for both axes (got {conv.padding})")
+    ops.check_same_conv(conv.weight.shape[2], conv.weight.shape[3], int(ph))
+    return int(ph)
+
+
 def conv2d(x, conv, x2=None, mode=PLAIN, residual=None):
-    """nn.Conv2d(stride 1, padding conv.padding) of the logical input formed by `mode`.  Under
+    """nn.Conv2d(stride 1, padding conv.padding) of the logical input formed by `mode` (conv_pad: modules
+    the kernels do not implement raise ValueError).  Under
     precision("bf16") the dense contractions (K = cin*kh*kw >= 64, cout >= 16: every conv but the
     7x7 single-channel stem and the single-channel output) run on the bf16 matrix cores (weights
     packed once per (tensor, version); ops.clear_bf16_packs() after in-place `.data` updates)."""
-    pad = conv.padding[0] if isinstance(conv.padding, tuple) else int(conv.padding)
+    pad = conv_pad(conv)
     return torch.ops.red_diffeq.conv2d_mfma(x, x2, conv.weight, conv.bias, residual, pad, mode,
                                             _PREC["mode"] == "bf16")
 

@@ -678,6 +678,15 @@ def clear_bf16_packs():
     _BF16_PACKS.clear()
 
 
+def check_same_conv(kh, kw, pad):
+    """The conv kernels write an H x W output with one `pad` for both axes (include/red_diffeq_unet.h, the contract
+    of rdq_conv_desc): nn.Conv2d's result exactly when 2 pad = k - 1 on both axes.  Anything else is refused
+    here, before any device work, instead of computing something that is not the module's convolution."""
+    if 2 * pad != kh - 1 or 2 * pad != kw - 1:
+        raise ValueError(f"conv kernels implement 'same' convolutions only: a {kh} x {kw} filter with padding {pad} "
+                         f"is not nn.Conv2d's H x W result (need kh = kw = 2 * pad + 1)")
+
+
 def bf16_eligible(weight):
     cout, cin, kh, kw = weight.shape
     return cin * kh * kw >= 64 and cout >= 16
@@ -687,7 +696,9 @@ def bf16_eligible(weight):
 def conv2d_mfma(x: Tensor, x2: Optional[Tensor], weight: Tensor, bias: Optional[Tensor], residual: Optional[Tensor],
                 pad: int, mode: int, bf16: bool) -> Tensor:
     """nn.Conv2d (stride 1) of the logical input cat(x', x2), x' = x | upsample2(x) | unshuffle2(x)
-    (mode 0 / 1 / 2), + bias + residual; fp32 MFMA, or bf16 operands with fp32 accumulation."""
+    (mode 0 / 1 / 2), + bias + residual; fp32 MFMA, or bf16 operands with fp32 accumulation.
+    ValueError unless kh = kw = 2 pad + 1 (check_same_conv)."""
+    check_same_conv(weight.shape[2], weight.shape[3], pad)
     _hip.require_device(x)
     x = x.contiguous()
     x2 = x2.contiguous() if x2 is not None else None

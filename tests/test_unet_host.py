@@ -526,7 +526,8 @@ def test_entry_point_rejects(fn, what, changes):
 def test_every_unet_entry_point_with_arguments_has_rejections():
     """The table covers every launching entry point of include/red_diffeq_unet.h."""
     header = open(os.path.join(ROOT, "include", "red_diffeq_unet.h")).read()
-    launching = set(re.findall(r"^int (rdq_\w+)\(", header, re.M)) - {"rdq_unet_set_option", "rdq_unet_options_generation"}
+    launching = set(re.findall(r"^int (rdq_\w+)\(", header, re.M)) - {"rdq_unet_set_option", "rdq_unet_options_generation",
+                                                                      "rdq_conv2d_route"}   # host queries: no launch
     assert launching == set(VALID) == {fn for fn, _, _ in REJECTED}
     for fn, args in VALID.items():
         assert len(args) == len(_hip.SIGNATURES[fn][1]), fn
