@@ -217,6 +217,23 @@ int rdq_rmsnorm(int32_t B, int32_t C, int32_t HW, const float *x, const float *g
 int rdq_linear(int32_t B, int32_t in, int32_t out, const float *x, const float *w, const float *bias,
                int32_t act_in, int32_t act_out, float *y, hipStream_t stream);
 
+/* Which kernel rdq_time_mlp (B) and rdq_linear_silu_multi (B, in) launch (pure host functions; the two entry
+ * points branch on them, so a test knows which kernel it compared).  Per sample every route computes the
+ * PER_SAMPLE route's result bit for bit.
+ *   PER_SAMPLE  a workgroup (time MLP) or a wave (a linear's row) per sample: k_time_mlp, k_linear_silu_multi
+ *   BATCHED     the samples of a block share the staged operands: k_time_mlp_b (B > 16),
+ *               k_linear_silu_multi_b (B > 16, in < 256)
+ *   WDOT        rdq_linear_silu_multi only, B > 16 and in = 256: a sample per lane (k_wdot_silu_b)
+ * INVALID for B < 1 or in < 1. */
+typedef enum rdq_linear_route {
+    RDQ_LINEAR_ROUTE_INVALID = 0,
+    RDQ_LINEAR_ROUTE_PER_SAMPLE = 1,
+    RDQ_LINEAR_ROUTE_BATCHED = 2,
+    RDQ_LINEAR_ROUTE_WDOT = 3
+} rdq_linear_route;
+int rdq_time_mlp_route(int32_t B);
+int rdq_linear_silu_multi_route(int32_t B, int32_t in);
+
 /* Unet.time_mlp in one launch (diffusion.py:255-258): y = W2 GELU(W1 SinusoidalPosEmb(t) + b1) + b2,
  * w1 [hid][dim], w2 [out][hid]; one workgroup per sample. */
 int rdq_time_mlp(int32_t B, int32_t dim, float theta, const int64_t *t, const float *w1, const float *b1, int32_t hid,

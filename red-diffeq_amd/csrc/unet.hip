@@ -4376,6 +4376,22 @@ int rdq_sinusoidal_emb(int32_t B, int32_t dim, float theta, const int64_t *t, fl
     return 0;
 }
 
+// the one place that picks the time MLP's kernel and the multi-linear's: rdq_time_mlp and
+// rdq_linear_silu_multi branch on these
+int rdq_time_mlp_route(int32_t B)
+{
+    if (B < 1) return RDQ_LINEAR_ROUTE_INVALID;
+    return B > 2 * TMB ? RDQ_LINEAR_ROUTE_BATCHED : RDQ_LINEAR_ROUTE_PER_SAMPLE;
+}
+
+int rdq_linear_silu_multi_route(int32_t B, int32_t in)
+{
+    if (B < 1 || in < 1) return RDQ_LINEAR_ROUTE_INVALID;
+    if (B > LSB / 2 && in == 256) return RDQ_LINEAR_ROUTE_WDOT;
+    if (B > LSB / 2 && in <= 256) return RDQ_LINEAR_ROUTE_BATCHED;
+    return RDQ_LINEAR_ROUTE_PER_SAMPLE;
+}
+
 int rdq_time_mlp(int32_t B, int32_t dim, float theta, const int64_t *t, const float *w1, const float *b1, int32_t hid,
                  const float *w2, const float *b2, int32_t out, float *y, hipStream_t st)
 {
@@ -4383,7 +4399,7 @@ int rdq_time_mlp(int32_t B, int32_t dim, float theta, const int64_t *t, const fl
         !t || !w1 || !b1 || !w2 || !b2 || !y)
         return RDQ_E_INVALID;
     const TmArgs m{dim, hid, out, -sinusoidal_step(dim, theta), t, w1, b1, w2, b2, y};
-    if (B > 2 * TMB)
+    if (rdq_time_mlp_route(B) == RDQ_LINEAR_ROUTE_BATCHED)
         hipLaunchKernelGGL(k_time_mlp_b, dim3((out + 4 * TMB_RW - 1) / (4 * TMB_RW), (B + TMB - 1) / TMB), dim3(256),
                            TMB * (dim + hid) * sizeof(float), st, m, B);
     else
@@ -4399,10 +4415,11 @@ int rdq_linear_silu_multi(int32_t B, int32_t in, const float *x, int32_t n, cons
     LinMulti L;
     if (B < 1 || in < 1 || !x || n < 1 || n > LM_MAX || !w || !out || !y || !lin_multi(L, n, w, b, out, y))
         return RDQ_E_INVALID;
-    if (B > LSB / 2 && in == 256)
+    const int route = rdq_linear_silu_multi_route(B, in);
+    if (route == RDQ_LINEAR_ROUTE_WDOT)
         hipLaunchKernelGGL(k_wdot_silu_b, dim3((L.start[n] + 4 * WDR - 1) / (4 * WDR), (B + 63) / 64), dim3(256), 0, st, B,
                            x, L);
-    else if (B > LSB / 2 && in <= 256)
+    else if (route == RDQ_LINEAR_ROUTE_BATCHED)
         hipLaunchKernelGGL(k_linear_silu_multi_b, dim3((L.start[n] + 4 * LSR - 1) / (4 * LSR), (B + LSB - 1) / LSB),
                            dim3(256), LSB * in * sizeof(float), st, in, B, x, L);
     else

@@ -199,6 +199,8 @@ SIGNATURES = {
     "rdq_rmsnorm": (c_int32, [c_int32, c_int32, c_int32, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p]),
     "rdq_linear": (c_int32, [c_int32, c_int32, c_int32, c_void_p, c_void_p, c_void_p, c_int32, c_int32, c_void_p,
                              c_void_p]),
+    "rdq_time_mlp_route": (c_int32, [c_int32]),
+    "rdq_linear_silu_multi_route": (c_int32, [c_int32, c_int32]),
     "rdq_time_mlp": (c_int32, [c_int32, c_int32, c_float, c_void_p, c_void_p, c_void_p, c_int32, c_void_p, c_void_p,
                                c_int32, c_void_p, c_void_p]),
     "rdq_linear_silu_multi": (c_int32, [c_int32, c_int32, c_void_p, c_int32, c_void_p, c_void_p, c_void_p, c_void_p,

@@ -527,7 +527,35 @@ def test_every_unet_entry_point_with_arguments_has_rejections():
     """The table covers every launching entry point of include/red_diffeq_unet.h."""
     header = open(os.path.join(ROOT, "include", "red_diffeq_unet.h")).read()
     launching = set(re.findall(r"^int (rdq_\w+)\(", header, re.M)) - {"rdq_unet_set_option", "rdq_unet_options_generation",
-                                                                      "rdq_conv2d_route"}   # host queries: no launch
+                                                                      "rdq_conv2d_route", "rdq_time_mlp_route",
+                                                                      "rdq_linear_silu_multi_route"}   # host queries: no launch
     assert launching == set(VALID) == {fn for fn, _, _ in REJECTED}
     for fn, args in VALID.items():
         assert len(args) == len(_hip.SIGNATURES[fn][1]), fn
+    for fn in ("rdq_time_mlp_route", "rdq_linear_silu_multi_route"):
+        assert fn in _hip.SIGNATURES and re.search(rf"^int {fn}\(", header, re.M), fn
+
+
+# RDQ_LINEAR_ROUTE_* (include/red_diffeq_unet.h)
+LIN_INVALID, PER_SAMPLE, BATCHED, WDOT = 0, 1, 2, 3
+# B -> rdq_time_mlp_route
+TIME_MLP_ROUTES = {0: LIN_INVALID, -3: LIN_INVALID, 1: PER_SAMPLE, 2: PER_SAMPLE, 16: PER_SAMPLE, 17: BATCHED,
+                   25: BATCHED, 344: BATCHED}
+# (B, in) -> rdq_linear_silu_multi_route
+LSM_ROUTES = {(0, 256): LIN_INVALID, (2, 0): LIN_INVALID, (1, 256): PER_SAMPLE, (16, 256): PER_SAMPLE,
+              (16, 64): PER_SAMPLE, (17, 1): BATCHED, (17, 64): BATCHED, (17, 255): BATCHED, (344, 100): BATCHED,
+              (17, 256): WDOT, (65, 256): WDOT, (344, 256): WDOT, (17, 257): PER_SAMPLE, (20, 600): PER_SAMPLE,
+              (344, 1024): PER_SAMPLE}
+
+
+def test_linear_route_queries():
+    """The routing of rdq_time_mlp and rdq_linear_silu_multi as the header states it: the batched kernels from 17
+    samples, the sample-per-lane kernel at in = 256 only, the per-sample kernel for in > 256 at any B."""
+    lib = _hip.load_library()
+    header = open(os.path.join(ROOT, "include", "red_diffeq_unet.h")).read()
+    for name, v in (("INVALID", LIN_INVALID), ("PER_SAMPLE", PER_SAMPLE), ("BATCHED", BATCHED), ("WDOT", WDOT)):
+        assert re.search(rf"RDQ_LINEAR_ROUTE_{name} = {v}\b", header), name
+    for B, want in TIME_MLP_ROUTES.items():
+        assert lib.rdq_time_mlp_route(B) == want, B
+    for (B, cin), want in LSM_ROUTES.items():
+        assert lib.rdq_linear_silu_multi_route(B, cin) == want, (B, cin)
