@@ -209,6 +209,19 @@ int rdq_fwi_set_adjoint_role(rdq_fwi_plan *plan, int32_t mode);
  * role's loop: one per workgroup whose interior rows own the source row; the word is zeroed by every
  * persistent adjoint call. */
 int rdq_fwi_adjoint_role_info(rdq_fwi_plan *plan, int32_t B, int32_t out[2]);
+/* How the adjoint's source/receiver role fetches its receiver residuals and wavelet samples; mode 0 / 1, default
+ * 1 (RDQ_E_INVALID for any other mode, nothing changed):
+ *   0: an epoch ahead: the T residuals and T samples of the next epoch, issued after the hand-off sweep;
+ *   1: the residuals a step ahead: step k issues step k - 1's residual ahead of its own history prefetch, the
+ *      epoch's last step that of the next epoch's first step; a step's head, where the residual goes into the
+ *      rows the neighbouring waves wait for, then finds a value issued a whole step earlier.  The samples,
+ *      read at a step's end, stay an epoch ahead.
+ * Only the role's loop differs (launches without the role run the same kernels whatever is set); the values
+ * loaded are the same: results are bit-identical in both modes.  Changing the mode drops the plan's cached
+ * graphs. */
+int rdq_fwi_set_adjoint_fetch(rdq_fwi_plan *plan, int32_t mode);
+/* *out = the fetch mode the adjoint of a call with batch B runs: 0 wherever the role does not run. */
+int rdq_fwi_adjoint_fetch_info(rdq_fwi_plan *plan, int32_t B, int32_t *out);
 /* The mirrored row pair (0..2) the role uses for padded row `padded_row` (>= 0; host only, no plan). */
 int rdq_fwi_role_row_pair(int32_t padded_row);
 /* 1 (default) = run each time loop as ONE persistent launch (regions resident in registers for

@@ -2880,7 +2880,14 @@ __global__ __launch_bounds__(64 * NW) void k_adj_pt(AdjPtArgs a)
     }
 #define ADJR_STEP_NB(CUR, PRV, P0, P1, P2, PN)                                                      \
     {                                                                                               \
-        if constexpr (RL_PLAIN) {                    /* steady epoch: every prefetched slot exists */ \
+        if constexpr (RL_SR >= 0 && SA) {            /* step-ahead fetch: the next step's residual */ \
+            dv[(t + 1) % T] = DLOAD(k - 1);                                                         \
+            /* the history prefetch without its `grad` test (the role's wave owns an interior row; a halo    \
+               lane's offset is out of range and loads 0): under the test the in-order wait for the load     \
+               above is placed for the path without the six loads, vmcnt(3) at the next step's head, and     \
+               the wave waits there for history it needs a step later (1.366 -> 1.401 ms) */                 \
+            ADJR_LOAD(PN, HRe, (T - 1 - t) * L4)                                                    \
+        } else if constexpr (RL_PLAIN) {             /* steady epoch: every prefetched slot exists */ \
             if (grad) ADJR_LOAD(PN, HRe, (T - 1 - t) * L4)                                          \
         } else if (ldall || (grad && k >= 2)) ADJR_LOAD(PN, HRe, (T - 1 - t) * L4)                  \
         const float dcur = dv[t];                                                                   \
@@ -2903,7 +2910,15 @@ __global__ __launch_bounds__(64 * NW) void k_adj_pt(AdjPtArgs a)
 // 1.4911 -> 1.4722, kernel_ab_adj_shadow_fwd_xmfirst.jsonl).  In the forward the zeroing in the round
 // trip was slower (1.011 -> 1.035 ms: more stale first passes) and the lean form after the sweep no
 // faster, so the forward has the one order.
-template <int T, int NW, int RW, bool PROF, int OV = 0, int SR = -1>
+// SA (rdq_fwi_set_adjoint_fetch), with a role only (SR >= 0): false = the role's loop loads its T residuals and
+// wavelet samples an epoch ahead, after the sweep (ADJ_ISSUE); true = the residuals a step ahead: step k loads
+// step k - 1's ahead of its own history prefetch, the epoch's last step the next epoch's first (ADJR_STEP_NB),
+// so a step's head, where the residual goes into the boundary rows its neighbours wait for, finds a value
+// issued a whole step earlier instead of one issued a few instructions earlier, at the end of the tail.  The
+// wavelet samples, read at a step's end, stay an epoch ahead: with them a step ahead too the overlap-1 builds
+// spill two VGPR values (profiles/r26/resource_usage.txt).  The bound (no such loads at all) is 84-86 of the 1360
+// us, the residuals alone take 81: 1.3599 -> 1.2784 ms at configs[1] (profiles/r26/kernel_ab_adj_fetch.jsonl).
+template <int T, int NW, int RW, bool PROF, int OV = 0, int SR = -1, bool SA = false>
 __global__ __launch_bounds__(64 * NW) void k_adj_pr(AdjPtArgs a)
 {
     unsigned long long *const prof = PROF ? a.prof : nullptr;   // phase counters: profiled build only
@@ -2913,6 +2928,7 @@ __global__ __launch_bounds__(64 * NW) void k_adj_pr(AdjPtArgs a)
     constexpr int RL_SR = -1, SRP = 0;                    // source/receiver role: the row's pair (SRP = max(RL_SR, 0))
     constexpr bool PR_S = SR >= 0;                        // history row offsets as scalars (ADJR_LOAD)
     static_assert(SR < RW / 2 && (SR < 0 || (T == PT_ROLES_T && RW == PT_SROLE_RW)), "k_adj_pr: the role's row pair");
+    static_assert(SR >= 0 || !SA, "k_adj_pr: the step-ahead fetch belongs to the role's loop");
     __shared__ XmBox<NW> xm;                              // the waves' inboxes (xm_*)
     __shared__ double red[64 * NW];
     // the LDS the residency decision (resident_capacity) depends on: the mailboxes and the reduction
@@ -3052,7 +3068,10 @@ __global__ __launch_bounds__(64 * NW) void k_adj_pr(AdjPtArgs a)
             if constexpr (OV == 0) PT_SWEEP(GR, tag, L0, L1, PT_ADJ_SG)                             \
             else PT_SWEEP_SHADOW(GR, tag, L0, L1, PT_ADJ_SG, (PT_ADJ_SG < R ? PT_ADJ_SG : R))       \
             xm_put<NW>(xm, (e + 1) * T & 1, w, lane, (unsigned)((e + 1) * T) + 1u, A[0] * L1[0], A[1] * L1[1]); \
-            if constexpr (!RL_PLAIN || RL_SR >= 0) ADJ_ISSUE                                        \
+            if constexpr (!RL_PLAIN || (RL_SR >= 0 && !SA)) ADJ_ISSUE                               \
+            else if constexpr (RL_SR >= 0) {         /* step-ahead: the residuals come with the steps */ \
+                _Pragma("unroll") for (int t = 0; t < T; ++t) wv[t] = a.wav[max(kn - t - 1, 0)];     \
+            }                                                                                       \
             PT_PROF_TAIL                                                                            \
         }                                                                                           \
         if constexpr ((T & 3) != 0) {                                                               \
@@ -3102,6 +3121,10 @@ __global__ __launch_bounds__(64 * NW) void k_adj_pr(AdjPtArgs a)
             if (lane == 0)                                // once per wave and launch: the role ran
                 __hip_atomic_fetch_add(a.status + PT_ROLE_WORD, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
             for (; e + 1 < nep; ++e) ADJR_EPOCH
+            if constexpr (SA) {                           // the generic epoch's samples and residuals, as the plain branch
+                const int kn = a.nt - e * T;
+                ADJ_ISSUE
+            }
         }
     }
     for (; e < nep; ++e) ADJR_EPOCH
@@ -3501,6 +3524,8 @@ constexpr int RDQ_SWEEP_DELAY_FWD = 15, RDQ_SWEEP_DELAY_ADJ = 0;
 constexpr int RDQ_OVERLAP_ADJ = 1, PT_OV_T = 4;
 // default source-role mode of the persistent forward (rdq_fwi_set_source_role)
 constexpr int RDQ_SROLE_FWD = 1;
+// default fetch mode of the adjoint's source/receiver role (rdq_fwi_set_adjoint_fetch): the residuals a step ahead
+constexpr int RDQ_ADJ_FETCH = 1;
 
 struct rdq_fwi_plan {
     rdq_fwi_geom g;
@@ -3533,6 +3558,7 @@ struct rdq_fwi_plan {
     int adj_roles = 1;              // wave roles of the persistent (recurrence) adjoint (rdq_fwi_set_wave_roles)
     int fwd_srole = RDQ_SROLE_FWD;  // source role of the persistent forward (rdq_fwi_set_source_role)
     int adj_srole = 1;              // source/receiver role of the persistent adjoint (rdq_fwi_set_adjoint_role)
+    int adj_fetch = RDQ_ADJ_FETCH;  // that role's residual / sample fetch: 0 an epoch ahead, 1 a step ahead (rdq_fwi_set_adjoint_fetch)
     int adj_Tw = 0;             // the wide chunked adjoint's depth (<= TW_ADJ_MAXT); 0 = auto, see wide_adj_depth
     int fwd_Tw = 0;             // the wide chunked forward's depth (<= TW_FWD_MAXT); 0 = auto, see wide_fwd_depth
     int adj_spw = 0;            // the wide chunked adjoint's shots per workgroup, 0 = auto (wide_spw)
@@ -3962,13 +3988,16 @@ int adjoint_role_pair(const rdq_fwi_plan *p, int NW, bool prof)
     if (!source_role_fits(p, NW, p->adj_T, p->adj_rw)) return -1;
     return role_row_pair(p->g.isz);
 }
-template <int OV>
+// The fetch mode of the role's residuals and wavelet samples (rdq_fwi_set_adjoint_fetch; k_adj_pr's SA) that a
+// launch with the role runs.
+int adjoint_fetch(const rdq_fwi_plan *p, int NW, bool prof) { return adjoint_role_pair(p, NW, prof) >= 0 ? p->adj_fetch : 0; }
+template <int OV, bool SA>
 KernelRef<AdjPtArgs> adj_pr_role(int sr)
 {
     constexpr int T = PT_ROLES_T, RW = PT_SROLE_RW;
-    if (sr == 0) return {k_adj_pr<T, 16, RW, false, OV, 0>, 64 * 16};
-    if (sr == 1) return {k_adj_pr<T, 16, RW, false, OV, 1>, 64 * 16};
-    return {k_adj_pr<T, 16, RW, false, OV, 2>, 64 * 16};
+    if (sr == 0) return {k_adj_pr<T, 16, RW, false, OV, 0, SA>, 64 * 16};
+    if (sr == 1) return {k_adj_pr<T, 16, RW, false, OV, 1, SA>, 64 * 16};
+    return {k_adj_pr<T, 16, RW, false, OV, 2, SA>, 64 * 16};
 }
 KernelRef<AdjPtArgs> adj_pt_kernel(const rdq_fwi_plan *p, int NW, int T, bool fma, bool prof)
 {
@@ -3976,7 +4005,8 @@ KernelRef<AdjPtArgs> adj_pt_kernel(const rdq_fwi_plan *p, int NW, int T, bool fm
     static_assert(PT_ROLES_T == 4 && PT_SROLE_RW / 2 == 3, "adj_pr_role: the role's depth and its three row pairs");
     if (T == p->adj_T && fma == p->adj_fma) {
         const int sr = adjoint_role_pair(p, NW, prof);
-        if (sr >= 0) return adj_overlap(p) ? adj_pr_role<1>(sr) : adj_pr_role<0>(sr);
+        if (sr >= 0 && adjoint_fetch(p, NW, prof)) return adj_overlap(p) ? adj_pr_role<1, true>(sr) : adj_pr_role<0, true>(sr);
+        if (sr >= 0) return adj_overlap(p) ? adj_pr_role<1, false>(sr) : adj_pr_role<0, false>(sr);
     }
     if (T == 4 && fma && adj_overlap(p))
         return prof ? adj_pt_T<4, true, 1>(NW, p->adj_rw, true) : adj_pt_T<4, false, 1>(NW, p->adj_rw, true);
@@ -4880,6 +4910,23 @@ int rdq_fwi_adjoint_role_info(rdq_fwi_plan *p, int32_t B, int32_t out[2])
     const int nwa = persistent_nw(p, B, true);
     out[1] = nwa ? adjoint_role_pair(p, nwa, p->d_prof != nullptr) : -1;
     out[0] = out[1] >= 0 ? 1 : 0;
+    return 0;
+}
+
+int rdq_fwi_set_adjoint_fetch(rdq_fwi_plan *p, int32_t mode)
+{
+    if (!p || mode < 0 || mode > 1) return RDQ_E_INVALID;
+    std::lock_guard<std::mutex> lk(p->mu);
+    set_knob(p, p->adj_fetch, mode);   // (drops the cached graphs when the value changes)
+    return 0;
+}
+
+int rdq_fwi_adjoint_fetch_info(rdq_fwi_plan *p, int32_t B, int32_t *out)
+{
+    if (!p || !out || B < 1) return RDQ_E_INVALID;
+    std::lock_guard<std::mutex> lk(p->mu);
+    const int nwa = persistent_nw(p, B, true);
+    *out = nwa ? adjoint_fetch(p, nwa, p->d_prof != nullptr) : 0;
     return 0;
 }
 

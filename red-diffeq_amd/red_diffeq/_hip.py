@@ -89,6 +89,8 @@ SIGNATURES = {
     "rdq_fwi_source_role_info": (c_int32, [c_void_p, c_int32, ctypes.POINTER(c_int32)]),
     "rdq_fwi_set_adjoint_role": (c_int32, [c_void_p, c_int32]),
     "rdq_fwi_adjoint_role_info": (c_int32, [c_void_p, c_int32, ctypes.POINTER(c_int32)]),
+    "rdq_fwi_set_adjoint_fetch": (c_int32, [c_void_p, c_int32]),
+    "rdq_fwi_adjoint_fetch_info": (c_int32, [c_void_p, c_int32, ctypes.POINTER(c_int32)]),
     "rdq_fwi_role_row_pair": (c_int32, [c_int32]),
     "rdq_fwi_profile_split": (c_int32, [c_void_p, ctypes.POINTER(ctypes.c_uint64)]),
     "rdq_fwi_profile_waves_split": (c_int32, [c_void_p, c_int32, ctypes.POINTER(ctypes.c_uint64), c_size_t]),

@@ -181,7 +181,8 @@ class FwiPlan:
         'adj_overlap' (the hand-off overlap mode that runs, set_handoff_overlap), 'fwd_roles' /
         'adj_roles' (the wave-role mode that runs, set_wave_roles), 'fwd_src_role' / 'adj_src_role' (the
         source-role mode that runs, set_source_role), 'adj_role' / 'adj_role_pair' (the adjoint-role mode that
-        runs, set_adjoint_role, and the row pair it runs with, -1 = none)} of a
+        runs, set_adjoint_role, and the row pair it runs with, -1 = none), 'adj_fetch' (the fetch mode of that role's
+        residuals and samples that runs, set_adjoint_fetch: 0 wherever the role does not run)} of a
         call with batch B (launches: time-loop kernel launches per call)."""
         out = (ctypes.c_int32 * 10)()
         _hip.check(self.lib.rdq_fwi_launch_info(self.handle, int(B), out), "rdq_fwi_launch_info")
@@ -189,13 +190,16 @@ class FwiPlan:
         _hip.check(self.lib.rdq_fwi_source_role_info(self.handle, int(B), src), "rdq_fwi_source_role_info")
         arole = (ctypes.c_int32 * 2)()
         _hip.check(self.lib.rdq_fwi_adjoint_role_info(self.handle, int(B), arole), "rdq_fwi_adjoint_role_info")
+        fetch = ctypes.c_int32()
+        _hip.check(self.lib.rdq_fwi_adjoint_fetch_info(self.handle, int(B), ctypes.byref(fetch)),
+                   "rdq_fwi_adjoint_fetch_info")
         return {"fwd_persistent": bool(out[0]), "adj_persistent": bool(out[1]),
                 "fwd_class": int(out[0]), "adj_class": int(out[1]), "fwd_T": int(out[2]),
                 "adj_T": int(out[3]), "fwd_launches": int(out[4]), "adj_launches": int(out[5]),
                 "fwd_overlap": int(out[6]), "adj_overlap": int(out[7]),
                 "fwd_roles": int(out[8]), "adj_roles": int(out[9]),
                 "fwd_src_role": int(src[0]), "adj_src_role": int(src[1]),
-                "adj_role": int(arole[0]), "adj_role_pair": int(arole[1])}
+                "adj_role": int(arole[0]), "adj_role_pair": int(arole[1]), "adj_fetch": int(fetch.value)}
 
     def set_sweep_delay(self, fwd_ticks, adj_ticks):
         """Persistent kernels: 10 ns ticks between an epoch's publish and its first hand-off pass."""
@@ -232,6 +236,13 @@ class FwiPlan:
         the host picks), 0 = the generic loop.  launch_info reports the mode that runs.  Results are
         bit-identical in both modes."""
         _hip.check(self.lib.rdq_fwi_set_adjoint_role(self.handle, int(mode)), "rdq_fwi_set_adjoint_role")
+
+    def set_adjoint_fetch(self, mode):
+        """The adjoint's source/receiver role (set_adjoint_role): 0 = the role's wave loads an epoch's
+        receiver residuals and wavelet samples after the previous epoch's hand-off sweep, 1 (default) = the residuals a
+        step ahead, each step the next step's ahead of its own history prefetch (the samples as in mode 0).  launch_info reports the mode that runs (0
+        without the role).  Results are bit-identical in both modes."""
+        _hip.check(self.lib.rdq_fwi_set_adjoint_fetch(self.handle, int(mode)), "rdq_fwi_set_adjoint_fetch")
 
     def adjoint_role_waves(self):
         """Waves that entered the adjoint's source/receiver loop in the last persistent adjoint call

@@ -29,6 +29,6 @@ flags = ["--offload-arch=gfx950", "-O3", "-std=c++17", "-fPIC", "-I" + os.path.j
 subprocess.check_call(["/opt/rocm/bin/hipcc", *flags, "-c", "-o", obj, hip])
 os.makedirs(os.path.join(PKG, "lib_exp"), exist_ok=True)
 out = os.path.join(PKG, "lib_exp", f"lib{name}.so")
-others = [os.path.join(PKG, "build", f"{o}.o") for o in ("fwi", "unet", "loop") if o != which]
+others = [os.path.join(PKG, "build", f"{o}.o") for o in ("fwi", "unet", "loop", "misfit") if o != which]
 subprocess.check_call(["/opt/rocm/bin/hipcc", "--offload-arch=gfx950", "-shared", "-o", out, obj, *others])
 print(out)

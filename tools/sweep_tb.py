@@ -8,7 +8,9 @@ summary line with the bar a mode has to pass (every run faster than every baseli
 apart by at least three times the larger min-max spread).  --roles F,A sets the wave-role modes;
 --ab-knob roles makes --ab alternate wave-role mode pairs instead (e.g. --ab-modes "0,0;1,1"); --srole F,A sets
 the source-role modes and --ab-knob srole alternates those (e.g. --ab-modes "0,0;1,1"); --arole M sets the
-adjoint's source/receiver role and --ab-knob arole alternates it (--ab-modes "0,0;0,1": the forward's half is 0)."""
+adjoint's source/receiver role and --ab-knob arole alternates it (--ab-modes "0,0;0,1": the forward's half is 0);
+--afetch M sets that role's fetch mode (0 an epoch ahead, 1 a step ahead) and --ab-knob afetch alternates it
+(--ab-modes "0;1", or "0,0;0,1")."""
 import argparse
 import json
 import os
@@ -36,10 +38,11 @@ ap.add_argument("--delay", default=None, help="pre-sweep delays of the persisten
 ap.add_argument("--overlap", default=None, help="hand-off overlap modes of the persistent kernels, 'fwd,adj'")
 ap.add_argument("--ab", type=int, default=0, help="rounds of an alternated A/B of hand-off overlap modes")
 ap.add_argument("--ab-modes", default="0,0;0,1", help="'fwd,adj' mode pairs of the A/B, baseline first")
-ap.add_argument("--ab-knob", default="overlap", choices=["overlap", "roles", "srole", "arole"], help="the setting --ab alternates")
+ap.add_argument("--ab-knob", default="overlap", choices=["overlap", "roles", "srole", "arole", "afetch"], help="the setting --ab alternates")
 ap.add_argument("--roles", default=None, help="wave-role modes of the persistent kernels, 'fwd,adj'")
 ap.add_argument("--srole", default=None, help="source-role modes of the persistent kernels, 'fwd,adj'")
 ap.add_argument("--arole", type=int, default=None, help="source/receiver role of the persistent adjoint, 0 / 1")
+ap.add_argument("--afetch", type=int, default=None, help="fetch mode of the adjoint's source/receiver role, 0 / 1")
 a = ap.parse_args()
 dev = torch.device("cuda:0")
 ctx = dict(n_grid=70, nt=a.nt, dx=10.0, dt=0.001, nbc=120, f=15.0, sz=10, gz=10, ng=70, ns=a.ns)
@@ -58,6 +61,8 @@ if a.srole:
     plan.set_source_role(*[int(x) for x in a.srole.split(",")])
 if a.arole is not None:
     plan.set_adjoint_role(a.arole)
+if a.afetch is not None:
+    plan.set_adjoint_fetch(a.afetch)
 sz = plan.sizes(a.B)
 dseis = torch.randn(a.B, a.ns, sz.nrec, plan.ng, device=dev)
 
@@ -86,11 +91,13 @@ if a.ab:
     plan.set_tuning(4, 4, 1)
     plan.set_persistent(a.mode)
     pairs = [tuple(int(x) for x in m.split(",")) for m in a.ab_modes.split(";")]
+    pairs = [(0,) + m if len(m) == 1 else m for m in pairs]   # (a bare adjoint mode: the forward's half is 0)
     runs = {m: [] for m in pairs}
     timed(a.reps)                                         # warm-up (clocks, allocator), not recorded
     setter = {"overlap": plan.set_handoff_overlap, "roles": plan.set_wave_roles, "srole": plan.set_source_role,
-              "arole": lambda f, m: plan.set_adjoint_role(m)}[a.ab_knob]   # (the adjoint's alone: the forward's half is 0)
-    key = {"srole": "src_role", "arole": "role"}.get(a.ab_knob, a.ab_knob)
+              "arole": lambda f, m: plan.set_adjoint_role(m),   # (the adjoint's alone: the forward's half is 0)
+              "afetch": lambda f, m: plan.set_adjoint_fetch(m)}[a.ab_knob]
+    key = {"srole": "src_role", "arole": "role", "afetch": "fetch"}.get(a.ab_knob, a.ab_knob)
     for rnd in range(a.ab):
         for m in pairs:
             setter(*m)
@@ -145,6 +152,7 @@ for T, G in cfgs:
                 "roles": [plan.launch_info(a.B).get("fwd_roles", 0), plan.launch_info(a.B).get("adj_roles", 0)],
                 "srole": [plan.launch_info(a.B).get("fwd_src_role", 0), plan.launch_info(a.B).get("adj_src_role", 0)],
                 "arole": [plan.launch_info(a.B).get("adj_role", 0), plan.launch_info(a.B).get("adj_role_pair", -1)],
+                "afetch": plan.launch_info(a.B).get("adj_fetch", 0),
                 "fwd_launches": plan.launch_info(a.B)["fwd_launches"], "fwd_ms": round(fw, 3), "adj_ms": round(ad, 3),
                 "shot_ts_per_s": round(a.ns * a.nt * a.B / ((fw + ad) * 1e-3))})
     if a.profile and G:
