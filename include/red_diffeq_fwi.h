@@ -511,6 +511,41 @@ int rdq_fwi_grad_finalize_enc(const rdq_fwi_plan *plan, int32_t B, int32_t ne, c
                               const float *gbeta, int32_t vel_mode, double *colsum, float *g_v,
                               hipStream_t stream);
 
+/* Source illumination / pseudo-Hessian diagonal (Shin et al.): the diagonal of J_A^T J_A with the Green's functions
+ * dropped, per wavefield.  With C1X2 = -5, C2 = fp32(4/3), C3 = fp32(-1/12) and S1 / S2 the nearest / second-neighbour
+ * sums with periodic wrap, ((up + down) + left) + right:
+ *
+ *   q_k[b,w,z,x] = C1X2 P_{k-1} + (C2 S1(P_{k-1}) + C3 S2(P_{k-1}))    fp32, one rounding per operation, no contraction:
+ *                                                                       the factor the adjoint multiplies L_k by for gA
+ *   hA[b,w,z,x]  = sum_{k = nt .. 1} q_k^2                              fp32: t = q q; acc = acc + t; k DESCENDING from 0
+ *   H[b,iz,ix]   = (dA/dv)^2 sum_{(z,x) -> (iz,ix)} sum_w hA[b,w,z,x]   fp64: ascending w, then the replicate fold (the
+ *                                                                       padded cells whose clamped index is (iz,ix), the
+ *                                                                       set K4 folds gA over), one cast to fp32
+ *   dA/dv        = 2 v (dt/dx)^2 in fp64, v the model cell's fp32 velocity in m/s; x 1500 under RDQ_VEL_NORMALIZED
+ *
+ * The sponge (gk) and source-amplitude (gbeta) paths of the Jacobian are left out, and so is the receiver side.
+ *
+ * rdq_fwi_illum: hA from a stored history [nt+2][B][nwf][Hp][ld] written by any forward family (persistent, wide,
+ * narrow, _src, _enc); nwf = the history's wavefields per model, 0 = the plan's ns.  hA has the size and layout of
+ * rdq_fwi_sizes(B).gA (rdq_fwi_sizes_enc(B, nwf).gA for nwf wavefields) and is overwritten: every element of
+ * [B][nwf][Hp][0..Wp) is written whatever the buffer held, the pitch columns are neither read nor written, and the
+ * history's pitch columns are never read.
+ * rdq_fwi_illum_ckpt: the same bits from the checkpoint store of rdq_fwi_forward_ckpt / _src / _enc /
+ * rdq_fwi_born_fused with K steps per segment: segments from the last to the first, each recomputed into `seg` by the
+ * forward the matching rdq_fwi_adjoint_ckpt{,_src,_enc} call would run (src / enc: that call's, at most one of them),
+ * then accumulated in k = hi .. lo + 1.  ckpt may be NULL when K >= nt (one segment).
+ * rdq_fwi_illum_finalize: H [B][nz][nx] (contiguous) from hA; colsum is rdq_fwi_sizes(B).colsum bytes of workspace.
+ * Stream-ordered on caller-owned buffers, one call per plan at a time, graph-cached like the passes above.
+ * RDQ_E_INVALID: a null required pointer, B < 1, nwf < 0, K < 1, both src and enc, an unusable src / enc, a missing
+ * ckpt with more than one segment, a vel_mode other than 0 / 1. */
+int rdq_fwi_illum(const rdq_fwi_plan *plan, int32_t B, int32_t nwf, const float *history, float *hA,
+                  hipStream_t stream);
+int rdq_fwi_illum_ckpt(const rdq_fwi_plan *plan, int32_t B, int32_t K, const float *coeffs,
+                       const rdq_fwi_source *src, const rdq_fwi_encoding *enc, const float *ckpt, float *seg,
+                       float *ring, float *hA, hipStream_t stream);
+int rdq_fwi_illum_finalize(const rdq_fwi_plan *plan, int32_t B, int32_t nwf, const float *coeffs, const float *hA,
+                           int32_t vel_mode, double *colsum, float *H, hipStream_t stream);
+
 /* K5: L1 observation loss (red_diffeq/core/losses.py:14-41), contiguous [B][n] operands.
  * forward:  loss[b] = sum(|y - pred| * mask) / nobs[b],  nobs[b] = max(sum(mask), 1)
  * backward: dpred = sign(pred - y) * mask * (gout[b] / nobs[b])       (mask NULL = all ones)

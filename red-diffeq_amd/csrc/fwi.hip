@@ -924,6 +924,100 @@ __global__ __launch_bounds__(64 * TB_NW, 4) void k_adj_tb(AdjTBArgs a)
     if (tid == 0) a.gk_part[(size_t)bs * a.nblk + ti.tile] += red[0];
 }
 
+// --------------------------------------------------------------------------------------- Illumination
+// Source illumination / pseudo-Hessian diagonal (rdq_fwi_illum, include/red_diffeq_fwi.h): per wavefield and padded
+// cell,
+//   hA = sum_{k = first, first - 1, ...} q_k^2,   q_k = 2c1 P_{k-1} + (c2 S1(P_{k-1}) + c3 S2(P_{k-1})),
+// q_k the factor k_adj_tb multiplies L_k by for gA (tb_lap's star of P, then d = C1X2 P; d = d + lap), every
+// operation a separate fp32 rounding: t = q q; acc = acc + t, k descending.  The term of step k needs level k of
+// the history only, so the pass is a stream over the levels with no temporal blocking: the depth-1 region of the
+// narrow kernels (64 columns x 8 waves x 8 rows, halo 2, interior 60 x 60, tiles_x / tiles_y at T = 1), the
+// vertical taps through the LDS exchange (one barrier per level) and the horizontal ones through DPP, as
+// k_fwd_tb.  The loads of IL_DEPTH levels are in flight per wave (a register ring, indexed statically by the
+// unrolled loop); a level past the launch's last gets a zero-length buffer descriptor (no memory access, zeros),
+// so no load sits behind a branch.  The column of a lane is wrapped into [0, Wp): the history's pitch columns are
+// never read, and hA is read and written on the tile's interior only (columns < Wp).  `init`: the call's first
+// launch on these wavefields starts from zero instead of reading hA, so the result does not depend on what hA held.
+constexpr int IL_DEPTH = 4;              // levels of history loads in flight per wave
+__device__ __forceinline__ float bload_nt(__amdgpu_buffer_rsrc_t r, int voff, int soff);   // (with the persistent adjoint)
+struct IllumTBArgs {
+    TBGeo g;
+    const float *hist;                   // slot k = P_{k-1}
+    float *hA;                           // [B][nwf][Hp][ld]
+    int first, nsteps;                   // steps first, first - 1, ... (nsteps of them)
+    int hbase;                           // virtual slot held by hist's first level (FwdTBArgs::hbase)
+    int init;                            // 1: start from zero, 0: continue from hA
+};
+
+__global__ __launch_bounds__(64 * TB_NW) void k_illum_tb(IllumTBArgs a)
+{
+    constexpr int H = 2, IW = 64 - 2 * H, IH = TB_RH - 2 * H;
+    __shared__ float xch[2][TB_NW][4][64];
+    const TBGeo &g = a.g;
+    const int lane = threadIdx.x & 63;
+    const int w = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
+    const TileId ti = decode_tile(blockIdx.x, g.tiles_x, g.ntiles, g.B * g.ns_grp);
+    if (!ti.valid) return;                                            // whole workgroup: uniform
+    const int b = ti.sl / g.ns_grp, s = g.s_off + (ti.sl - b * g.ns_grp), bs = b * g.ns + s;
+    const int ux = ti.tx * IW - H + lane;
+    const int gx = wrapn(ux, g.Wp);
+    const bool xin = lane >= H && lane < 64 - H && ux < g.Wp;
+    const int uz0 = ti.ty * IH - H + w * TB_R;
+    const size_t so = (size_t)bs * g.slice;
+    float acc[TB_R];
+    int pofs[TB_R];
+    unsigned rin = 0;                    // wave-uniform mask of the interior rows
+#pragma unroll
+    for (int r = 0; r < TB_R; ++r) {
+        const int uz = uz0 + r, gz = wrapn(uz, g.Hp);
+        const int rr = w * TB_R + r;
+        pofs[r] = (gz * g.ld + gx) * 4;
+        if (rr >= H && rr < TB_RH - H && uz < g.Hp) rin |= 1u << r;
+        acc[r] = (!a.init && (rin & (1u << r)) && xin) ? a.hA[so + (size_t)gz * g.ld + gx] : 0.0f;
+    }
+    const int slice_bytes = (int)(g.slice * 4);
+    // level of step k: slot k (P_{k-1}); t >= nsteps: a zero-length descriptor
+    auto level_of = [&](int t) {
+        const int tc = t < a.nsteps ? t : 0;
+        return rsrc_of(a.hist + (size_t)(a.first - tc - a.hbase) * g.level + so, t < a.nsteps ? slice_bytes : 0);
+    };
+    float Pq[IL_DEPTH][TB_R];
+#pragma unroll
+    for (int u = 0; u < IL_DEPTH; ++u) {
+        const __amdgpu_buffer_rsrc_t HR = level_of(u);
+#pragma unroll
+        for (int r = 0; r < TB_R; ++r) Pq[u][r] = bload_nt(HR, pofs[r], 0);
+    }
+    for (int t0 = 0; t0 < a.nsteps; t0 += IL_DEPTH) {
+#pragma unroll
+        for (int u = 0; u < IL_DEPTH; ++u) {
+            const int t = t0 + u;
+            if (t >= a.nsteps) break;                                 // uniform
+            float P[TB_R];
+#pragma unroll
+            for (int r = 0; r < TB_R; ++r) P[r] = Pq[u][r];
+            {
+                const __amdgpu_buffer_rsrc_t HR = level_of(t + IL_DEPTH);
+#pragma unroll
+                for (int r = 0; r < TB_R; ++r) Pq[u][r] = bload_nt(HR, pofs[r], 0);
+            }
+            const Halo4 h4 = exchange_nw<TB_NW>(xch, t & 1, w, lane, P[0], P[1], P[TB_R - 2], P[TB_R - 1]);
+#pragma unroll
+            for (int r = 0; r < TB_R; ++r) {
+                const float lap = tb_lap(P, r, h4);                   // every lane active (DPP)
+                float d = C1X2 * P[r]; d = d + lap;
+                const float q2 = d * d;
+                acc[r] = acc[r] + q2;                                 // (halo cells too: never stored)
+            }
+        }
+    }
+    if (xin) {
+#pragma unroll
+        for (int r = 0; r < TB_R; ++r)
+            if (rin & (1u << r)) a.hA[so + (size_t)(pofs[r] >> 2)] = acc[r];
+    }
+}
+
 // --------------------------------------------------------------------------------------- Born
 // Linearised forward J dv (rdq_fwi_born).  The tangent of the time step in the direction dv,
 //   dP_{n+1} = T1 dP_n - T2 dP_{n-1} + A Lap(dP_n) + dA (2c1 P_n + Lap(P_n)) - dK (P_n - P_{n-1}) + dbeta_src w[n],
@@ -3344,6 +3438,64 @@ __global__ __launch_bounds__(256) void k_fin_cols(FinArgs p)
     p.out[(size_t)b * p.nz * p.nx + i] = (float)(acc * p.scale);
 }
 
+// Illumination finalize (rdq_fwi_illum_finalize): H[b, iz, ix] = (dA/dv)^2 sum_{(z, x) -> (iz, ix)} sum_w hA[b, w, z, x],
+// dA/dv = 2 v (dt/dx)^2 (x 1500 for normalised input), v the model cell's fp32 velocity (field 5 of K3: every padded
+// cell of the fold holds the same value).  Everything in fp64: the wavefield planes in ascending w, then K4's
+// two-stage replicate fold (rows into colsum [B][Hp][nx], then columns), one cast to fp32 at the end.  Two square
+// factors of dA/dv, which is why this is not K4 with zeroed gk / gbeta.
+struct IllumFinArgs {
+    int B, nwf, nz, nx, nbc, Hp, Wp, ld;
+    float dt, dx;
+    double scale;     // d(v)/d(input): 1500 for normalised input, 1 for physical velocity
+    size_t cstride, slice;
+    const float *coeffs, *hA;
+    double *colsum;   // [B][Hp][nx]
+    float *out;       // [B][nz][nx]
+};
+__global__ __launch_bounds__(256) void k_illum_fin_rows(IllumFinArgs p)
+{
+    __shared__ double hs[FIN_MAXW];
+    const int z = blockIdx.x, b = blockIdx.y;
+    const float *HA = p.hA + (size_t)b * p.nwf * p.slice + (size_t)z * p.ld;
+    for (int x = threadIdx.x; x < p.Wp; x += blockDim.x) {
+        double acc = 0.0;
+        int s = 0;
+        for (; s + 4 <= p.nwf; s += 4) {     // loads issued 4 at a time, added in order
+            float v[4];
+#pragma unroll
+            for (int u = 0; u < 4; ++u) v[u] = HA[(size_t)(s + u) * p.slice + x];
+#pragma unroll
+            for (int u = 0; u < 4; ++u) acc += (double)v[u];
+        }
+        for (; s < p.nwf; ++s) acc += (double)HA[(size_t)s * p.slice + x];
+        hs[x] = acc;
+    }
+    __syncthreads();
+    double *CS = p.colsum + ((size_t)b * p.Hp + z) * p.nx;
+    for (int ix = threadIdx.x; ix < p.nx; ix += blockDim.x) {
+        const int x0 = ix == 0 ? 0 : ix + p.nbc, x1 = ix == p.nx - 1 ? p.Wp : ix + p.nbc + 1;
+        double acc = 0.0;
+        for (int x = x0; x < x1; ++x) acc += hs[x];
+        CS[ix] = acc;
+    }
+}
+__global__ __launch_bounds__(256) void k_illum_fin(IllumFinArgs p)
+{
+    const int i = blockIdx.x * blockDim.x + threadIdx.x;
+    const int b = blockIdx.y;
+    if (i >= p.nz * p.nx) return;
+    const int iz = i / p.nx, ix = i - iz * p.nx;
+    const int z0 = iz == 0 ? 0 : iz + p.nbc;
+    const int z1 = iz == p.nz - 1 ? p.Hp : iz + p.nbc + 1;
+    const double *cs = p.colsum + (size_t)b * p.Hp * p.nx + ix;
+    double acc = 0.0;
+    for (int z = z0; z < z1; ++z) acc += cs[(size_t)z * p.nx];
+    const double v = (double)p.coeffs[5 * p.cstride + (size_t)b * p.slice + (size_t)(iz + p.nbc) * p.ld + (ix + p.nbc)];
+    const double r = (double)p.dt / (double)p.dx;
+    const double d = 2.0 * v * (r * r) * p.scale;
+    p.out[(size_t)b * p.nz * p.nx + i] = (float)((d * d) * acc);
+}
+
 // --------------------------------------------------------------------------------------- K5
 constexpr int L1_BLOCK = 256;
 constexpr int L1_ITEMS = 16;   // elements per thread per block tile
@@ -4319,20 +4471,24 @@ __global__ __launch_bounds__(256) void k_ckpt_levels(const float *src, float *ds
 //             launch ending on an interior boundary writes its pair into the checkpoint store and the next reads
 //             it there); the dP pair (in2 / out2) always ping-pongs in ring levels 4-7.  Narrow kernels at the
 //             forward's narrow depth and chains, as born.
+//   illum_hist  the illumination pass over a stored history: one k_illum_tb launch per chain over slots 1 .. nt;
+//   illum_ckpt  adj_ckpt's schedule with the adjoint launches of a segment replaced by one illumination launch
+//             over slots lo + 1 .. hi: the levels, the fwd_hist recompute, then illum (the first segment visited,
+//             the last in time, starts the accumulator from zero).
 // A call with its own wavelets (`src`: rdq_fwi_*_src) runs the same four passes on the narrow kernels' SRC
 // instantiations at the narrow depths and chains, as born does; the wavelet and gwav indices are absolute, so a
 // segment's recompute reads the samples the first pass read.
 // The adjoint's levels stay in the ring between launches and the ring parity runs on across segments.
 // Every launch of a chain is ordered on the chain's stream, so a segment's recompute overwrites the
 // segment buffer only after the previous segment's adjoint has read it.
-enum class Pass { fwd_ring, fwd_hist, adj_hist, adj_ckpt, born, fwd_born };
+enum class Pass { fwd_ring, fwd_hist, adj_hist, adj_ckpt, born, fwd_born, illum_hist, illum_ckpt };
 enum class Store { none, ring, ckpt, hist };
 struct LevelPair {                   // two consecutive levels {slot, slot + 1} of a store (none: nullptr)
     Store store;
     int slot;
 };
 struct Launch {
-    enum Kind { levels, fwd, adj, born, fwd_born } kind;
+    enum Kind { levels, fwd, adj, born, fwd_born, illum } kind;
     int chain, s_off, ns_sh;         // launch chain and its shots [s_off, s_off + ns_sh) of every model
     int first, nsteps;               // fwd: steps first, first + 1, ...; adj: steps first, first - 1, ...
     int seg, hbase;                  // segment, and the slot held by the history buffer's first level
@@ -4349,7 +4505,8 @@ bool narrow_pass(Pass pass) { return pass == Pass::born || pass == Pass::fwd_bor
 std::vector<Launch> chunked_schedule(const rdq_fwi_plan *p, int B, Pass pass, const CkptPlan &cp, bool src = false,
                                      int nwf = 0)
 {
-    const bool wide = p->wide && !narrow_pass(pass) && !src;
+    const bool wide = p->wide && !narrow_pass(pass) && !src, wide_pass = wide;
+    const bool illum = pass == Pass::illum_hist || pass == Pass::illum_ckpt;
     const int Tf = wide ? wide_fwd_depth(p) : p->fwd_T, Ta = wide ? wide_adj_depth(p) : p->adj_T;
     const int ns = nwf > 0 ? nwf : p->g.ns, S = chain_count(p, wide, ns);
     std::vector<Launch> sched;
@@ -4362,8 +4519,8 @@ std::vector<Launch> chunked_schedule(const rdq_fwi_plan *p, int B, Pass pass, co
         if (kind != Launch::levels) {
             // tile grid of this launch's depth (the wide kernels run a short tail as its own depth); wide
             // kernels: spw shots of one region per workgroup (the decode's slice groups are shot groups)
-            const bool adj = kind == Launch::adj;
-            const int Tl = wide ? nsteps : (adj ? Ta : Tf);
+            const bool adj = kind == Launch::adj, wide = wide_pass && kind != Launch::illum;   // (k_illum_tb: the narrow depth-1 grid)
+            const int Tl = kind == Launch::illum ? 1 : wide ? nsteps : (adj ? Ta : Tf);
             l.tiles_x = wide ? tw_tiles_x(p->Wp, Tl) : tiles_x(p->Wp, Tl);
             l.ntiles = l.tiles_x * (wide ? tw_tiles_y(p->Hp, Tl, adj) : tiles_y(p->Hp, Tl));
             l.spw = wide ? wide_spw(adj ? p->adj_spw : p->fwd_spw, B * l.ntiles, l.ns_sh, adj, S) : 1;
@@ -4393,14 +4550,16 @@ std::vector<Launch> chunked_schedule(const rdq_fwi_plan *p, int B, Pass pass, co
         }
         for (int sg = 0; sg < cp.nseg; ++sg) {
             const int lo = cp.lo(sg), hi = cp.hi(sg);
-            if (pass == Pass::adj_ckpt)   // slots lo, lo + 1: checkpoint sg + 1 = pair sg, or zeros at the record's start
+            if (pass == Pass::adj_ckpt || pass == Pass::illum_ckpt)   // slots lo, lo + 1: checkpoint sg + 1 = pair sg, or zeros at the record's start
                 add(Launch::levels, c, sg, lo, 0, lo > 0 ? LevelPair{Store::ckpt, 2 * sg} : LevelPair{Store::none, 0},
                     LevelPair{Store::hist, 0});
-            if (pass != Pass::adj_hist)   // slot n0 = P_{n0-1}, slot n0 + 1 = P_{n0}; writes slots lo + 2 .. hi + 1
+            if (pass != Pass::adj_hist && pass != Pass::illum_hist)   // slot n0 = P_{n0-1}, slot n0 + 1 = P_{n0}; writes slots lo + 2 .. hi + 1
                 for (int n0 = lo; n0 < hi; n0 += Tf)
                     add(Launch::fwd, c, sg, n0, std::min(Tf, hi - n0), LevelPair{Store::hist, n0 - lo},
                         LevelPair{Store::none, 0});
-            if (pass != Pass::fwd_hist)   // adjoint steps k = hi .. lo + 1: slots lo + 1 .. hi
+            if (illum)                    // steps k = hi .. lo + 1 in one launch: slots lo + 1 .. hi
+                add(Launch::illum, c, sg, hi, hi - lo, LevelPair{Store::none, 0}, LevelPair{Store::none, 0});
+            else if (pass != Pass::fwd_hist)   // adjoint steps k = hi .. lo + 1: slots lo + 1 .. hi
                 for (int k0 = hi; k0 > lo; k0 -= Ta, ++i) {
                     const int pin = i & 1, pout = pin ^ 1;
                     add(Launch::adj, c, sg, k0, std::min(Ta, k0 - lo), LevelPair{Store::ring, 2 * pin},
@@ -4425,7 +4584,7 @@ struct ChunkBufs {
     const float *coeffs;
     float *seis, *hist, *ckpt, *ring;
     const float *dseis;
-    float *gA;
+    float *gA;                       // (illum passes: hA)
     double *gk;
     float *gbeta;
     const float *dwork;              // born: the perturbation workspace (`seis` is then the linearised record)
@@ -4433,6 +4592,7 @@ struct ChunkBufs {
     const rdq_fwi_source *src;       // the call's own wavelets (rdq_fwi_*_src), or nullptr: the plan's
     const rdq_fwi_encoding *enc;     // the call's encoding (rdq_fwi_*_enc): ne wavefields per model, every buffer
                                      // above with ns replaced by ne, gbeta [B][ne][ns]; or nullptr
+    int nwf;                         // illum_hist: the history's wavefields per model (0: the plan's shots, or enc's ne)
 };
 
 // What every time-loop launch sets the same way in its kernel arguments: the launch's shots and tile grid, and the
@@ -4454,7 +4614,7 @@ void enc_stride_bits(float *w, long long stride)
 int enqueue_chunked(rdq_fwi_plan *p, int B, Pass pass, int K, const ChunkBufs &b, hipStream_t st)
 {
     const bool enc = b.enc != nullptr, src = b.src != nullptr || enc;
-    const int ns = enc ? b.enc->ne : p->g.ns;        // wavefields per model
+    const int ns = enc ? b.enc->ne : b.nwf > 0 ? b.nwf : p->g.ns;        // wavefields per model
     const std::vector<Launch> sched = chunked_schedule(p, B, pass, ckpt_plan(p, K), src, ns);
     FwdTBArgs f{};
     AdjTBArgs a{};
@@ -4464,6 +4624,21 @@ int enqueue_chunked(rdq_fwi_plan *p, int B, Pass pass, int K, const ChunkBufs &b
     const size_t L = a.g.level, slice = a.g.slice;
     const int S = chain_count(p, p->wide && !narrow_pass(pass) && !src, ns), nblk_alloc = gk_blocks(p);
     const bool adjoint = pass == Pass::adj_hist || pass == Pass::adj_ckpt;
+    const bool illum = pass == Pass::illum_hist || pass == Pass::illum_ckpt;
+    IllumTBArgs il{};
+    il.g = a.g; il.hist = b.hist; il.hA = b.gA;
+    if (illum) {     // every illumination launch before anything is enqueued: its levels lie in the buffer it reads
+        // (a stored history: slots 0 .. nt + 1; a segment buffer: K + 2 levels from hbase), its grid is the
+        // depth-1 tile grid of its shots, and each chain's first launch (and only that one) starts hA from zero
+        const int levels = pass == Pass::illum_hist ? p->g.nt + 2 : ckpt_plan(p, K).K + 2;
+        for (const Launch &l : sched)
+            if (l.kind == Launch::illum &&
+                (l.nsteps < 1 || l.first - l.nsteps + 1 - l.hbase < 1 || l.first - l.hbase >= levels || l.spw != 1 ||
+                 l.s_off < 0 || l.ns_sh < 1 || l.s_off + l.ns_sh > ns ||
+                 l.ntiles != tiles_x(p->Wp, 1) * tiles_y(p->Hp, 1) ||
+                 l.grid != (unsigned)((l.ntiles + 7) / 8 * 8 * B * l.ns_sh)))
+                return RDQ_E_INVALID;
+    }
     if (adjoint) {   // the gk_part one-writer invariant, on every adjoint launch, before anything is enqueued
         GkWriters writers((size_t)B * ns, nblk_alloc);
         for (const Launch &l : sched)
@@ -4477,6 +4652,7 @@ int enqueue_chunked(rdq_fwi_plan *p, int B, Pass pass, int K, const ChunkBufs &b
                               {b.gk, (size_t)B * ns * nblk_alloc * sizeof(double)},
                               {b.gbeta, (size_t)B * ns * (enc ? p->g.ns : 1) * sizeof(float)}}, st));
     else if (pass == Pass::fwd_hist) RDQ_TRY(zero_regions({{b.hist, 2 * L * sizeof(float)}}, st));
+    else if (illum) {}               // nothing to zero: k_ckpt_levels fills a segment's first levels, k_illum_tb starts hA
     else RDQ_TRY(zero_regions({{b.ring, (pass == Pass::fwd_born ? 8 : 4) * L * sizeof(float)}}, st));   // P, and dP in 4-7
     f.coeffs = a.coeffs = d.coeffs = u.coeffs = b.coeffs;
     f.cg = a.cg = d.cg = u.cg = coef_gen(p, B, b.coeffs);
@@ -4537,6 +4713,10 @@ int enqueue_chunked(rdq_fwi_plan *p, int B, Pass pass, int K, const ChunkBufs &b
             u.in_prev = level(l.in2, 0); u.in_cur = level(l.in2, 1);
             u.out_prev = level(l.out2, 0); u.out_cur = level(l.out2, 1);
             launch_kernel(fwd_born_tb_kernel(p->fwd_T, p->fwd_gen), l.grid, cs, u);
+        } else if (l.kind == Launch::illum) {
+            il.g.s_off = l.s_off; il.g.ns_grp = l.ns_grp; il.g.tiles_x = l.tiles_x; il.g.ntiles = l.ntiles;
+            il.first = l.first; il.nsteps = l.nsteps; il.hbase = l.hbase; il.init = l.seg == 0;
+            launch_kernel(KernelRef<IllumTBArgs>{k_illum_tb, 64 * TB_NW}, l.grid, cs, il);
         } else {
             launch_geo_and_wavelet(a.g, a.w, l, p->wavf);
             if (enc) enc_stride_bits(a.w, b.enc->enc_stride);
@@ -5375,6 +5555,58 @@ int rdq_fwi_adjoint_ckpt_enc(const rdq_fwi_plan *pc, int32_t B, int32_t K, const
     if (!encoding_ok(enc)) return RDQ_E_INVALID;
     return adjoint_ckpt_call(const_cast<rdq_fwi_plan *>(pc), B, K, coeffs, nullptr, ckpt, seg, dseis, ring, gA, gk,
                              gbeta, st, enc);
+}
+
+// Illumination over a stored history: one k_illum_tb launch per chain (graph kind 32; the key's K slot holds nwf)
+int rdq_fwi_illum(const rdq_fwi_plan *pc, int32_t B, int32_t nwf, const float *history, float *hA, hipStream_t st)
+{
+    rdq_fwi_plan *p = const_cast<rdq_fwi_plan *>(pc);
+    if (!p || !history || !hA || B < 1 || nwf < 0) return RDQ_E_INVALID;
+    const int nw = nwf > 0 ? nwf : p->g.ns;
+    std::lock_guard<std::mutex> lk(p->mu);
+    RDQ_TRY(plan_enter(p, st));
+    ChunkBufs b{};
+    b.hist = const_cast<float *>(history); b.gA = hA;
+    b.nwf = nw;
+    return run_cached(p, 32, B, {history, hA}, st,
+                      [&](hipStream_t s) { return enqueue_chunked(p, B, Pass::illum_hist, p->g.nt, b, s); }, nw);
+}
+
+// Illumination over a checkpoint store: per segment the recompute the matching adjoint_ckpt call runs, then one
+// k_illum_tb launch (graph kinds 33, + 8 / + 16 as the other passes)
+int rdq_fwi_illum_ckpt(const rdq_fwi_plan *pc, int32_t B, int32_t K, const float *coeffs, const rdq_fwi_source *src,
+                       const rdq_fwi_encoding *enc, const float *ckpt, float *seg, float *ring, float *hA,
+                       hipStream_t st)
+{
+    rdq_fwi_plan *p = const_cast<rdq_fwi_plan *>(pc);
+    if (!p || !coeffs || !seg || !ring || !hA || B < 1 || K < 1 || (src && enc)) return RDQ_E_INVALID;
+    if ((src && !source_ok(src)) || (enc && !encoding_ok(enc))) return RDQ_E_INVALID;
+    if (!ckpt && ckpt_plan(p, K).nseg > 1) return RDQ_E_INVALID;
+    std::lock_guard<std::mutex> lk(p->mu);
+    RDQ_TRY(plan_enter(p, st));
+    ChunkBufs b{};
+    b.coeffs = coeffs; b.hist = seg; b.ckpt = const_cast<float *>(ckpt); b.ring = ring; b.gA = hA; b.src = src; b.enc = enc;
+    return run_cached(p, 33 + (src ? 8 : 0) + (enc ? 16 : 0), B, {coeffs, ckpt, seg, ring, hA}, st,
+                      [&](hipStream_t s) { return enqueue_chunked(p, B, Pass::illum_ckpt, K, b, s); }, ckpt_plan(p, K).K,
+                      src, enc);
+}
+
+int rdq_fwi_illum_finalize(const rdq_fwi_plan *p, int32_t B, int32_t nwf, const float *coeffs, const float *hA,
+                           int32_t vel_mode, double *colsum, float *H, hipStream_t st)
+{
+    if (!p || !coeffs || !hA || !colsum || !H || B < 1 || nwf < 0 || (vel_mode != 0 && vel_mode != 1))
+        return RDQ_E_INVALID;
+    if (p->Wp > FIN_MAXW) return RDQ_E_INVALID;
+    IllumFinArgs a;
+    a.B = B; a.nwf = nwf > 0 ? nwf : p->g.ns; a.nz = p->g.nz; a.nx = p->g.nx; a.nbc = p->g.nbc;
+    a.Hp = p->Hp; a.Wp = p->Wp; a.ld = p->ld; a.dt = p->g.dt; a.dx = p->g.dx;
+    a.scale = vel_mode == 0 ? 1500.0 : 1.0;
+    a.slice = (size_t)p->Hp * p->ld; a.cstride = (size_t)B * a.slice;
+    a.coeffs = coeffs; a.hA = hA; a.colsum = colsum; a.out = H;
+    hipLaunchKernelGGL(k_illum_fin_rows, dim3(p->Hp, B), dim3(256), 0, st, a);
+    hipLaunchKernelGGL(k_illum_fin, dim3((p->g.nz * p->g.nx + 255) / 256, B), dim3(256), 0, st, a);
+    RDQ_CHECK(hipGetLastError());
+    return 0;
 }
 
 // K4 of the plain call (ne == 0) or of an encoded one

@@ -133,6 +133,11 @@ SIGNATURES = {
                                      c_void_p, c_void_p]),
     "rdq_fwi_grad_finalize": (c_int32, [c_void_p, c_int32, c_void_p, c_void_p, c_void_p, c_void_p,
                                         c_void_p, c_int32, c_void_p, c_void_p, c_void_p]),
+    "rdq_fwi_illum": (c_int32, [c_void_p, c_int32, c_int32, c_void_p, c_void_p, c_void_p]),
+    "rdq_fwi_illum_ckpt": (c_int32, [c_void_p, c_int32, c_int32, c_void_p, ctypes.POINTER(FwiSource),
+                                     ctypes.POINTER(FwiEncoding), c_void_p, c_void_p, c_void_p, c_void_p, c_void_p]),
+    "rdq_fwi_illum_finalize": (c_int32, [c_void_p, c_int32, c_int32, c_void_p, c_void_p, c_int32, c_void_p, c_void_p,
+                                         c_void_p]),
     "rdq_l1_partial_bytes": (c_size_t, [c_int32, c_int64]),
     "rdq_l1_forward": (c_int32, [c_int32, c_int64, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p,
                                  c_void_p, c_void_p]),

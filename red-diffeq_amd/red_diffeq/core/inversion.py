@@ -28,6 +28,7 @@ from tqdm.auto import tqdm
 from ..regularization.base import RegularizationMethod
 from ..utils.data_trans import add_noise_to_seismic, missing_trace
 from ..utils.data_trans import v_normalize
+from ..utils.precondition import illumination_weights, precondition_grad
 from ..utils.ssim import SSIM
 from .fused import CosineLR, FusedAdamClamp, metrics as fused_metrics
 from .losses import LossCalculator, check_misfit, global_norm
@@ -226,6 +227,17 @@ def k12_covers(ssim_loss):
     return True
 
 
+def check_precondition(kind, eps=1e-2, power=1.0, every=0):
+    """The preconditioning settings, checked (ValueError) before any device work."""
+    if kind not in (None, "illumination"):
+        raise ValueError(f"Unknown precondition: {kind!r} (None or 'illumination')")
+    if not float(eps) > 0:
+        raise ValueError(f"precondition_eps must be > 0, got {eps}")
+    if int(every) != every or int(every) < 0:
+        raise ValueError(f"precondition_every must be an integer >= 0, got {every}")
+    return kind, float(eps), float(power), int(every)
+
+
 class InversionEngine:
 
     # clean chunked iterations before a failed persistent operator is tried again (_FaultMonitor)
@@ -233,7 +245,16 @@ class InversionEngine:
 
     def __init__(self, diffusion_model, ssim_loss: SSIM, regularization: Optional[str] = None,
                  use_time_weight: bool = False, sigma_x0: float = 0.0001, fixed_timestep: int = None,
-                 show_progress: bool = True):
+                 show_progress: bool = True, precondition: Optional[str] = None, precondition_eps: float = 1e-2,
+                 precondition_power: float = 1.0, precondition_every: int = 0):
+        """precondition: None = no preconditioning, the previous path bit for bit; "illumination" = optimize()
+        multiplies the data term's gradient (after the ranks' sum; not the regulariser's) by
+        utils.precondition.illumination_weights(H, precondition_eps, precondition_power), H =
+        fwi_forward.illumination(model) computed at iteration 0 (precondition_every = 0) or again every
+        precondition_every iterations; sharded, H is summed over the process group first.  It draws no random numbers.
+        The four are plain attributes and may be changed between optimize() calls."""
+        self.precondition, self.precondition_eps, self.precondition_power, self.precondition_every = check_precondition(
+            precondition, precondition_eps, precondition_power, precondition_every)
         self.diffusion_model = diffusion_model
         # optional list: when set, optimize() appends mu's interior (a device copy, after Adam and
         # the clamp) at every iteration — the per-iteration model trajectory, for parity tests
@@ -251,12 +272,19 @@ class InversionEngine:
                  missing_number: int = 0, regularization: Optional[str] = None, process_group=None,
                  misfit: str = "l1", huber_delta: Optional[float] = None):
         check_misfit(misfit, huber_delta)
+        # data-term preconditioning is a setting of the engine (the constructor's keywords / these attributes), read
+        # here at every call
+        precondition, precondition_eps, precondition_power, precondition_every = check_precondition(
+            self.precondition, self.precondition_eps, self.precondition_power, self.precondition_every)
         if mu.shape[0] != y.shape[0]:
             raise ValueError("Batch size mismatch between velocity and seismic data")
         if regularization not in ["diffusion", "l2", "tv", "hybrid", None]:
             raise ValueError(f"Unknown regularization: {regularization}")
         if fwi_forward is None or not callable(fwi_forward):
             raise ValueError("fwi_forward must be a callable forward modeling function")
+        if precondition is not None and not callable(getattr(fwi_forward, "illumination", None)):
+            raise ValueError("precondition='illumination' needs an operator with an illumination(v) method "
+                             "(FWIForward)")
         fwi_forward = fwi_forward.to(self.device)
         if regularization is not None:
             rm = self.regularization_method
@@ -310,6 +338,8 @@ class InversionEngine:
         diffusion = regularization == "diffusion"
         overlap = diffusion and mu.is_cuda and not os.environ.get("RDQ_NO_OVERLAP")
         snaps = [None] * ts
+        weights = None                   # the preconditioner in force (precondition=None: never set)
+        every = int(precondition_every)
 
         pbar = tqdm(total=ts, desc="Optimizing", unit="step", disable=not self.show_progress)
         prog = _Progress(ts, len(keys) * B, self.device) if self.show_progress and mu.is_cuda else None
@@ -320,17 +350,29 @@ class InversionEngine:
                 k = monitor.first_fault(it - 2) if monitor is not None else None
                 if k is not None:
                     it = self._rewind(k, snaps, optimizer, scheduler, monitor, ts, pbar, trace, prog)
+                    weights = snaps[it][5]
                     continue
                 if monitor is not None:   # host state at the start of the iteration (for a replay)
                     monitor.maybe_repromote(it)
                     snaps[it] = (optimizer.t, scheduler.lr, scheduler.last_epoch, optimizer.lr,
-                                 torch.cuda.get_rng_state(mu.device) if diffusion else None)
+                                 torch.cuda.get_rng_state(mu.device) if diffusion else None, weights)
                 if diffusion:
                     noise_x0 = torch.randn(mu.shape, device=mu.device, dtype=mu.dtype)
                     x0_pred = mu + self.regularization_method.sigma_x0 * noise_x0
                 else:
                     x0_pred = mu
                 v_in = x0_pred[:, :, 1:-1, 1:-1]
+                if precondition is not None:
+                    # a refresh due at this iteration is computed here, also when the iteration is a replay (the
+                    # snapshot holds the weights in force at its start); the illumination's forward runs the
+                    # operator's kernels, so a failed persistent launch sets the same status word
+                    if weights is None or (every > 0 and it % every == 0):
+                        H = fwi_forward.illumination(v_in.detach())
+                        if sharded:
+                            H = H.contiguous()
+                            dist.all_reduce(H, op=dist.ReduceOp.SUM, group=process_group)
+                        weights = illumination_weights(H, precondition_eps, precondition_power)
+                    v_in = precondition_grad(v_in, weights)
                 if sharded:
                     v_in = grad_all_reduce(v_in, process_group, monitor)
                 if overlap:
@@ -393,6 +435,7 @@ class InversionEngine:
             if k is None:
                 break
             it = self._rewind(k, snaps, optimizer, scheduler, monitor, ts, pbar, trace, prog)
+            weights = snaps[it][5]
         pbar.close()
 
         H = hist_dev.cpu().numpy()
@@ -415,7 +458,7 @@ class InversionEngine:
         if prog is not None:
             prog.events[k:] = [None] * (ts - k)
             prog.shown = min(prog.shown, k - 1)
-        optimizer.t, scheduler.lr, scheduler.last_epoch, optimizer.lr, rng = snaps[k]
+        optimizer.t, scheduler.lr, scheduler.last_epoch, optimizer.lr, rng = snaps[k][:5]   # ([5]: the caller's weights)
         if rng is not None:
             torch.cuda.set_rng_state(rng, optimizer.param.device)
         pbar.n = k

@@ -34,6 +34,11 @@ torch.compile see them as ordinary operators instead of opaque ctypes calls.
         (FWIForward.forward(v, encoding=E)); built on enc_fwi_forward / enc_fwi_adjoint / enc_fwi_forward_ckpt /
         enc_fwi_adjoint_ckpt / enc_fwi_grad_finalize (rdq_fwi_*_enc).  (Named enc_fwi*, not fwi*_enc: the set of
         fwi* operators is pinned by the host tests.)
+    red_diffeq::illum_fwi(history, plan, B, nwf) -> hA / illum_fwi_ckpt(coeffs, ckpt, seg, plan, B, K) -> hA (and
+        illum_fwi_ckpt_src(coeffs, w, ...), illum_fwi_ckpt_enc(coeffs, weff, ...)) /
+        illum_fwi_finalize(coeffs, hA, plan, B, nwf, vel_mode) -> H
+        the source illumination / pseudo-Hessian diagonal (rdq_fwi_illum*; FWIForward.illumination; no autograd
+        formula).  (Named illum_fwi*, as enc_fwi*.)
   U-Net (include/red_diffeq_unet.h)
     conv2d_mfma, conv2d_rms, conv2d_gn_silu, conv2d_bf16_gn_silu, conv2d_bf16_gn_silu_out, conv2d_gn_silu_sc, conv2d_gn_silu_lsm, conv2d_gn_silu_out, unet_head,
     gn_silu, rmsnorm, linear, time_mlp, linear_silu_multi, sinusoidal_emb, linear_attn, linear_attn_block, attn,
@@ -489,6 +494,123 @@ def enc_fwi_grad_finalize(coeffs: Tensor, vstat: Tensor, gA: Tensor, gk: Tensor,
 
 @enc_fwi_grad_finalize.register_fake
 def _(coeffs, vstat, gA, gk, gbeta, plan, B, ne, vel_mode):
+    p = _plan(plan)
+    return coeffs.new_empty(B, 1, p.nz, p.nx)
+
+
+# ---- source illumination / pseudo-Hessian diagonal (rdq_fwi_illum / _illum_ckpt / _illum_finalize).  Functional, no
+# autograd formula.  (Named illum_fwi*, not fwi_illum*: the set of fwi* operators is pinned by the host tests.)
+def _illum_nwf(p, nwf):
+    if nwf < 0:
+        raise ValueError(f"illum_fwi: nwf must be 0 (the plan's shots) or >= 1, got {nwf}")
+    return p.ns if nwf == 0 else int(nwf)
+
+
+def _illum_sizes(p, B, nwf):
+    return p.sizes(B) if nwf == p.ns else p.sizes_enc(B, nwf)
+
+
+@torch.library.custom_op(f"{LIB}::illum_fwi", mutates_args=())
+def illum_fwi(history: Tensor, plan: int, B: int, nwf: int) -> Tensor:
+    """hA (B * nwf * Hp * ld,) = sum over the steps of q_k^2 from a stored history of nwf wavefields per model
+    (nwf = 0: the plan's shots)."""
+    p = _plan(plan)
+    _hip.require_device(history)
+    nw = _illum_nwf(p, nwf)
+    sz = _illum_sizes(p, B, nw)
+    if history.dtype != torch.float32 or history.numel() * 4 != sz.history or not history.is_contiguous():
+        raise ValueError(f"illum_fwi: history must be contiguous fp32 of {sz.history} bytes")
+    hA = _f32(sz.gA, history.device)
+    _hip.check(p.lib.rdq_fwi_illum(p.handle, B, nw, _hip.ptr(history), _hip.ptr(hA), _hip.stream_of(history)),
+               "rdq_fwi_illum")
+    return hA
+
+
+@illum_fwi.register_fake
+def _(history, plan, B, nwf):
+    p = _plan(plan)
+    return history.new_empty(int(_illum_sizes(p, B, _illum_nwf(p, nwf)).gA) // 4)
+
+
+def _run_illum_ckpt(op, coeffs, ckpt, seg, plan, B, K, w=None, enc=False):
+    """The one checkpointed illumination pass behind illum_fwi_ckpt{,_src,_enc}."""
+    p = _plan(plan)
+    _hip.require_device(coeffs, w, ckpt, seg)
+    ne = None
+    src = enc_s = None
+    if enc:
+        w, enc_s = _encoding(p, w, B)
+        ne = w.shape[1]
+    elif w is not None:
+        w, src = _source(p, w, B)
+    sz, cs = _sizes(p, B, ne), _ckpt_sizes(p, B, K, ne)
+    if ckpt.dtype != torch.float32 or seg.dtype != torch.float32 or ckpt.numel() * 4 != cs.ckpt \
+            or seg.numel() * 4 != cs.seg or not ckpt.is_contiguous() or not seg.is_contiguous():
+        raise ValueError(f"{op}: ckpt / seg must be contiguous fp32 of {cs.ckpt} / {cs.seg} bytes (K = {K})")
+    ring = _f32(sz.ring, coeffs.device)
+    hA = _f32(sz.gA, coeffs.device)
+    _hip.check(p.lib.rdq_fwi_illum_ckpt(p.handle, B, K, _hip.ptr(coeffs), ctypes.byref(src) if src is not None else None,
+                                        ctypes.byref(enc_s) if enc_s is not None else None,
+                                        _hip.ptr(ckpt) if ckpt.numel() else ctypes.c_void_p(0), _hip.ptr(seg),
+                                        _hip.ptr(ring), _hip.ptr(hA), _hip.stream_of(coeffs)), "rdq_fwi_illum_ckpt")
+    return hA
+
+
+def _fake_illum_ckpt(coeffs, plan, B, ne=None):
+    return coeffs.new_empty(int(_sizes(_plan(plan), B, ne).gA) // 4)
+
+
+@torch.library.custom_op(f"{LIB}::illum_fwi_ckpt", mutates_args=("seg",))
+def illum_fwi_ckpt(coeffs: Tensor, ckpt: Tensor, seg: Tensor, plan: int, B: int, K: int) -> Tensor:
+    """hA from fwi_forward_ckpt's store: every segment recomputed into the scratch `seg`, then accumulated."""
+    return _run_illum_ckpt("illum_fwi_ckpt", coeffs, ckpt, seg, plan, B, K)
+
+
+@illum_fwi_ckpt.register_fake
+def _(coeffs, ckpt, seg, plan, B, K):
+    return _fake_illum_ckpt(coeffs, plan, B)
+
+
+@torch.library.custom_op(f"{LIB}::illum_fwi_ckpt_src", mutates_args=("seg",))
+def illum_fwi_ckpt_src(coeffs: Tensor, w: Tensor, ckpt: Tensor, seg: Tensor, plan: int, B: int, K: int) -> Tensor:
+    """illum_fwi_ckpt over fwi_forward_ckpt_src's store (the recompute reads the source samples w again)."""
+    return _run_illum_ckpt("illum_fwi_ckpt_src", coeffs, ckpt, seg, plan, B, K, w=w)
+
+
+@illum_fwi_ckpt_src.register_fake
+def _(coeffs, w, ckpt, seg, plan, B, K):
+    return _fake_illum_ckpt(coeffs, plan, B)
+
+
+@torch.library.custom_op(f"{LIB}::illum_fwi_ckpt_enc", mutates_args=("seg",))
+def illum_fwi_ckpt_enc(coeffs: Tensor, weff: Tensor, ckpt: Tensor, seg: Tensor, plan: int, B: int, K: int) -> Tensor:
+    """illum_fwi_ckpt over enc_fwi_forward_ckpt's store of ne supershots (the recompute reads weff again)."""
+    return _run_illum_ckpt("illum_fwi_ckpt_enc", coeffs, ckpt, seg, plan, B, K, w=weff, enc=True)
+
+
+@illum_fwi_ckpt_enc.register_fake
+def _(coeffs, weff, ckpt, seg, plan, B, K):
+    return _fake_illum_ckpt(coeffs, plan, B, ne=weff.shape[1])
+
+
+@torch.library.custom_op(f"{LIB}::illum_fwi_finalize", mutates_args=())
+def illum_fwi_finalize(coeffs: Tensor, hA: Tensor, plan: int, B: int, nwf: int, vel_mode: int) -> Tensor:
+    """H (B, 1, nz, nx) = (dA/dv)^2 x the replicate fold of the nwf planes of hA (fp64 sums, one cast)."""
+    p = _plan(plan)
+    _hip.require_device(coeffs, hA)
+    nw = _illum_nwf(p, nwf)
+    sz = _illum_sizes(p, B, nw)
+    if hA.dtype != torch.float32 or hA.numel() * 4 != sz.gA or not hA.is_contiguous():
+        raise ValueError("illum_fwi_finalize: hA does not match the plan and nwf")
+    colsum = torch.empty(int(sz.colsum) // 8, dtype=torch.float64, device=coeffs.device)
+    out = torch.empty(B, 1, p.nz, p.nx, dtype=torch.float32, device=coeffs.device)
+    _hip.check(p.lib.rdq_fwi_illum_finalize(p.handle, B, nw, _hip.ptr(coeffs), _hip.ptr(hA), vel_mode, _hip.ptr(colsum),
+                                            _hip.ptr(out), _hip.stream_of(coeffs)), "rdq_fwi_illum_finalize")
+    return out
+
+
+@illum_fwi_finalize.register_fake
+def _(coeffs, hA, plan, B, nwf, vel_mode):
     p = _plan(plan)
     return coeffs.new_empty(B, 1, p.nz, p.nx)
 

@@ -376,6 +376,28 @@ class FwiPlan:
         seg = torch.empty(int(self.ckpt_sizes(B, K).seg) // 4, dtype=torch.float32, device=coeffs.device)
         return torch.ops.red_diffeq.fwi_adjoint_ckpt(coeffs, ckpt, seg, dseis, self.op_id, int(B), int(K))
 
+    # ---- source illumination / pseudo-Hessian diagonal (rdq_fwi_illum*) ----
+    def illum(self, hist, B, nwf=0):
+        """hA (flat [B][nwf][Hp][ld]) = sum_k q_k^2 over a store-all history of nwf wavefields per model (0: the
+        plan's shots), whichever forward family wrote it."""
+        return torch.ops.red_diffeq.illum_fwi(hist, self.op_id, int(B), int(nwf))
+
+    def illum_ckpt(self, coeffs, ckpt, B, K, w=None, weff=None):
+        """The same bits from a checkpoint store (forward_ckpt, or the _src / enc_ forms with their wavelets `w` /
+        effective wavelets `weff`): each segment recomputed, then accumulated; the segment buffer lives for the call."""
+        ne = None if weff is None else weff.shape[1]
+        cs = self.ckpt_sizes(B, K) if ne is None else self.ckpt_sizes_enc(B, ne, K)
+        seg = torch.empty(int(cs.seg) // 4, dtype=torch.float32, device=coeffs.device)
+        if weff is not None:
+            return torch.ops.red_diffeq.illum_fwi_ckpt_enc(coeffs, weff, ckpt, seg, self.op_id, int(B), int(K))
+        if w is not None:
+            return torch.ops.red_diffeq.illum_fwi_ckpt_src(coeffs, w, ckpt, seg, self.op_id, int(B), int(K))
+        return torch.ops.red_diffeq.illum_fwi_ckpt(coeffs, ckpt, seg, self.op_id, int(B), int(K))
+
+    def illum_finalize(self, coeffs, hA, B, vel_mode, nwf=0):
+        """H (B, 1, nz, nx) from hA: the nwf planes summed, the replicate fold, (dA/dv)^2."""
+        return torch.ops.red_diffeq.illum_fwi_finalize(coeffs, hA, self.op_id, int(B), int(nwf), int(vel_mode))
+
 
 def checkpoint_levels(nt, K):
     """Wavefield levels a checkpointed gradient with K steps per segment holds (include/red_diffeq_fwi.h):
@@ -765,6 +787,71 @@ class FWIForward(nn.Module):
             del hist
             g = plan.finalize(coeffs, vstat, gA, gk, gb, v.shape[0], vel_mode)
         return (g if pull is None else pull(g)).detach()
+
+    def illumination(self, v, wavelet=None, encoding=None, per_wavefield=False):
+        """Source illumination / pseudo-Hessian diagonal of the survey at the model v (Shin et al.):
+        H = (dA/dv)^2 sum over wavefields, padded cells of the model cell and time steps of q_k^2, with q_k = 2 c1
+        P_{k-1} + Lap(P_{k-1}) the virtual-source factor the adjoint multiplies its field by (include/
+        red_diffeq_fwi.h).  (B, 1, nz, nx) fp32, per normalised model unit squared with the fused denormalisation
+        and per (m/s)^2 with normalize=False; per_wavefield=True: (B, nwf, nz, nx), one plane per shot (or per
+        supershot of `encoding`), each finalised on its own.  Runs under no_grad: K3, a forward that keeps its
+        history (what forward(v, wavelet, encoding) would run), the streaming pass, the finalize; under checkpoint= /
+        history_budget_gb the checkpointed first pass and the pass over its recomputed segments, with the same
+        bits.  With shots=, this rank's shots only (sum the ranks' H).  The sponge and source-amplitude terms of the
+        Hessian diagonal and the receiver side are left out.  ValueError, before any device work, for a custom
+        v_denorm_func (an arbitrary callable has no diagonal chain rule: construct with normalize=False and pass
+        physical velocities) and for wrong shapes."""
+        if self.normalize and not self._fused_denorm():
+            raise ValueError("illumination: a custom v_denorm_func has no diagonal chain rule; construct FWIForward "
+                             "with normalize=False and pass physical velocities")
+        if not isinstance(v, torch.Tensor) or v.dim() != 4 or v.shape[1] != 1:
+            raise ValueError(f"illumination: expected v of shape (B,1,H,W), got {tuple(getattr(v, 'shape', ()))}")
+        E = self._call_encoding(v, encoding) if encoding is not None else None
+        w = self._call_wavelet(v, wavelet) if wavelet is not None else None
+        _hip.require_device(v)
+        with torch.no_grad():
+            v = v.detach().float()
+            vel_mode = 0 if self._fused_denorm() else 1
+            plan = self._plan(v.shape[2], v.shape[3], v.device, per_call=wavelet is not None)
+            self._last = plan
+            B, nwf, weff = v.shape[0], plan.ns, None
+            if w is not None:
+                w = w.detach()
+            if E is not None:
+                if w is None:
+                    w = torch.from_numpy(plan._wav).to(device=v.device, dtype=torch.float32).expand(B, plan.ns, plan.nt)
+                weff, nwf = E.detach().unsqueeze(-1) * w.unsqueeze(1), E.shape[1]
+            K = None
+            if isinstance(self.checkpoint, int):
+                K = self.checkpoint
+            elif self.history_budget_gb is not None:
+                sz = plan.sizes(B) if weff is None else plan.sizes_enc(B, nwf)
+                K = choose_checkpoint(plan.nt, sz.history // (plan.nt + 2), int(float(self.history_budget_gb) * 2 ** 30))
+            ops = torch.ops.red_diffeq
+            coeffs, _ = plan.coeffs(v, vel_mode)
+            if K is None:
+                if weff is not None:
+                    hist = ops.enc_fwi_forward(coeffs, weff, plan.op_id, B, True)[1]
+                elif w is not None:
+                    hist = ops.fwi_forward_src(coeffs, w, plan.op_id, B, True)[1]
+                else:
+                    hist = plan.forward(coeffs, B, True)[1]
+                hA = plan.illum(hist, B, nwf)
+                del hist
+            else:
+                if weff is not None:
+                    ckpt = ops.enc_fwi_forward_ckpt(coeffs, weff, plan.op_id, B, K)[1]
+                elif w is not None:
+                    ckpt = ops.fwi_forward_ckpt_src(coeffs, w, plan.op_id, B, K)[1]
+                else:
+                    ckpt = plan.forward_ckpt(coeffs, B, K)[1]
+                hA = plan.illum_ckpt(coeffs, ckpt, B, K, w=w if weff is None else None, weff=weff)
+                del ckpt
+            if not per_wavefield:
+                return plan.illum_finalize(coeffs, hA, B, vel_mode, nwf)
+            planes = hA.view(B, nwf, -1)
+            return torch.cat([plan.illum_finalize(coeffs, planes[:, j].contiguous().view(-1), B, vel_mode, 1)
+                              for j in range(nwf)], dim=1)
 
     def checkpoint_interval(self, plan, B):
         """Steps per segment of the checkpointed gradient a differentiable call with batch B runs, or None

@@ -16,7 +16,9 @@ inversion never calls); under torchrun (WORLD_SIZE > 1) the shots are sharded ov
 (one RCCL all-reduce of the data-term gradient per iteration) and rank 0 writes the
 results.  Two options the reference lacks, --misfit {l1,l2,huber,ncc} and --huber_delta (config keys
 optimization.misfit / optimization.huber_delta, both optional: without them the run is the reference's
-L1), choose the data misfit.
+L1), choose the data misfit; --precondition illumination (with --precondition_eps, --precondition_power,
+--precondition_every; config keys optimization.precondition*, all optional: without them no preconditioning) scales
+the data term's gradient by the inverse source illumination (red_diffeq/utils/precondition.py).
 """
 import argparse
 import os
@@ -108,6 +110,11 @@ def get_data_files(config) -> list:
     return picked
 
 
+def _precondition(config):
+    p = getattr(config.optimization, "precondition", None)
+    return p if p and p != "none" else None
+
+
 def process_batch(batch_start, batch_end, seis_mmap, vel_mmap, config, inversion_engine, fwi_forward, device):
     seis = torch.from_numpy(np.array(seis_mmap[batch_start:batch_end])).float().to(device)
     vel = torch.from_numpy(np.array(vel_mmap[batch_start:batch_end])).float()
@@ -152,7 +159,10 @@ def run_experiment(config) -> Path:
                              use_time_weight=getattr(config.optimization, "use_time_weight", False),
                              sigma_x0=getattr(config.optimization, "sigma_x0", 0.0001),
                              fixed_timestep=getattr(config.optimization, "fixed_timestep", None),
-                             show_progress=rank == 0)
+                             show_progress=rank == 0, precondition=_precondition(config),
+                             precondition_eps=getattr(config.optimization, "precondition_eps", 1e-2),
+                             precondition_power=getattr(config.optimization, "precondition_power", 1.0),
+                             precondition_every=getattr(config.optimization, "precondition_every", 0))
     seismic_dir = Path(config.data.seismic_data_dir).resolve()
     dataset = seismic_dir.parts[-2] if len(seismic_dir.parts) >= 2 else None
     stamp = datetime.now().strftime("%Y%m%d_%H%M%S")
@@ -200,6 +210,11 @@ def main(argv=None) -> None:
     p.add_argument("--missing_number", type=int)
     p.add_argument("--misfit", choices=list(MISFITS), help="data misfit (config: optimization.misfit, else l1)")
     p.add_argument("--huber_delta", type=float, help="threshold of --misfit huber (config: optimization.huber_delta)")
+    p.add_argument("--precondition", choices=["illumination", "none"],
+                   help="data-term preconditioner (config: optimization.precondition, else none)")
+    p.add_argument("--precondition_eps", type=float, help="floor of the normalised illumination (default 1e-2)")
+    p.add_argument("--precondition_power", type=float, help="exponent of the compensation (default 1)")
+    p.add_argument("--precondition_every", type=int, help="refresh period in iterations (default 0: once)")
     p.add_argument("--batch_size", type=int)
     p.add_argument("--experiment_name", type=str)
     p.add_argument("--results_dir", type=Path)
@@ -214,6 +229,10 @@ def main(argv=None) -> None:
                  "noise_std": ("optimization", "noise_std"), "sigma": ("optimization", "sigma"),
                  "sigma_x0": ("optimization", "sigma_x0"), "missing_number": ("optimization", "missing_number"),
                  "misfit": ("optimization", "misfit"), "huber_delta": ("optimization", "huber_delta"),
+                 "precondition": ("optimization", "precondition"),
+                 "precondition_eps": ("optimization", "precondition_eps"),
+                 "precondition_power": ("optimization", "precondition_power"),
+                 "precondition_every": ("optimization", "precondition_every"),
                  "batch_size": ("data", "batch_size"), "experiment_name": ("experiment", "name"),
                  "results_dir": ("experiment", "results_dir"), "random_seed": ("experiment", "random_seed"),
                  "openfwi_families": ("data", "openfwi_families"), "sample_index": ("data", "sample_index")}
